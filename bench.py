@@ -26,8 +26,20 @@ writer / deflate (no GPU anywhere), timed from BAM open to output close; the
 cores are the box's CPU quota (cgroup cpu.max).  Its ``kernels_only`` field
 is the restatement alone on the packed batch (no BAM I/O).
 
+A plain run (python bench.py --gpus 1 --steps K --warmup W) does only what
+value needs: it generates the families, writes the input BAM, runs the W + K
+CLI passes and prints the result line; roofline, config.device_resident,
+config.whole_node_level6_input and cpu_baseline are null in that line.
+--full adds the legs that take runs of their own: the device-resident
+roofline passes, the CPU baselines and the level-6 input passes.
+--kernel-only (value = the device-resident loop) runs that loop by itself.
+
+--dump-outputs DIR writes what the last timed CLI pass wrote, as .npy
+arrays (dump_outputs below); same arguments, same inputs, so two builds can
+be compared array for array.
+
 --config C3 / C4 / C5 runs the other BASELINE.json shapes (per-GPU shards).
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--full] [--dump-outputs DIR]
 (N > 1 is launched by torch.distributed.run, one process per GPU; every rank
 owns its own shard of families: weak scaling, no data-path collective.  C4
 at N > 1 deals one shared stream of N x 1,000 families to the ranks by LPT.)
@@ -385,6 +397,101 @@ def e2e_passes_sharded(path, params_args, steps, warmup, workdir, tdist, rank):
     return dt, stats
 
 
+DUMP_RECORDS = 1024          # records sampled per output BAM by --dump-outputs
+DUMP_BYTES = 4 << 20         # and at most this many record bytes per BAM (float32: 16 MiB; three BAMs < 64 MB)
+DUMP_SEED = 20
+CORE_FIELDS = ("block_size", "refID", "pos", "l_read_name", "mapq", "bin", "n_cigar_op", "flag", "l_seq",
+               "next_refID", "next_pos", "tlen")
+
+
+def bam_records(path):
+    """Every record of the BAM at ``path`` as bytes (length word included),
+    cut from 16 MiB reads of the decompressed stream; nothing is decoded."""
+    from duplexumiconsensusreads_amd import bam
+    f = bam.open_bgzf_reader(path)
+    buf, pos = b"", 0
+
+    def have(n):
+        # True once n bytes stand at pos; False at the end of the stream
+        nonlocal buf, pos
+        while len(buf) - pos < n:
+            more = f.read(1 << 24)
+            if not more:
+                return False
+            buf, pos = buf[pos:] + more, 0
+        return True
+
+    def skip(n):
+        nonlocal pos
+        if not have(n):
+            raise ValueError(f"{path}: truncated BAM header")
+        pos += n
+
+    def word():
+        skip(4)
+        return int.from_bytes(buf[pos - 4:pos], "little")
+
+    try:
+        if word() != int.from_bytes(b"BAM\x01", "little"):
+            raise ValueError(f"{path}: not a BAM file")
+        skip(word())                                # the header text
+        for _ in range(word()):
+            skip(word() + 4)                        # a reference's name and length
+        while have(4):
+            n = 4 + int.from_bytes(buf[pos:pos + 4], "little")
+            if not have(n):
+                break
+            yield buf[pos:pos + n]
+            pos += n
+        if len(buf) > pos:
+            raise ValueError(f"{path}: truncated BAM record at the end of the file")
+    finally:
+        f.close()
+
+
+def dump_outputs(out_dir, cons_path, suffix=""):
+    """--dump-outputs: what the last timed CLI pass gave its caller, the three
+    BAMs it wrote (consensus, filtered reads, filtered families), as arrays.
+    Per BAM ``name``:
+
+      name_summary.npy  float64 [2]: records in the file, bytes of all records
+      name_core.npy     float64 [S, 1 + 12]: the record's index in the file and
+                        its fixed fields (CORE_FIELDS), for a sample of S records
+      name_bytes.npy    float32 [sum of the S records' sizes]: every byte of
+                        the sampled records in file order (read name, CIGAR,
+                        sequence, qualities, tags)
+
+    The sample is fixed: DUMP_RECORDS indices drawn with DUMP_SEED from the
+    file's record count (all records of a smaller file), in file order, cut
+    where their bytes pass DUMP_BYTES.  A BAM without records (C2 filters
+    nothing) gives its summary alone: no empty array is written.  The BAM
+    header is left out (its @PG line holds the pass's output path)."""
+    import struct
+    os.makedirs(out_dir, exist_ok=True)
+    for name, path in (("consensus", cons_path), ("filteredreads", cons_path[:-4] + "_filteredreads.bam"),
+                       ("filteredfamilies", cons_path[:-4] + "_filteredfamilies.bam")):
+        n_rec = n_bytes = 0
+        for rec in bam_records(path):
+            n_rec += 1
+            n_bytes += len(rec)
+        rng = np.random.default_rng(DUMP_SEED)
+        want = np.sort(rng.choice(n_rec, DUMP_RECORDS, replace=False)) if n_rec > DUMP_RECORDS else np.arange(n_rec)
+        core, body, taken, k = [], [], 0, 0
+        for i, rec in enumerate(bam_records(path)):
+            if k == len(want) or taken + len(rec) > DUMP_BYTES:
+                break
+            if i == want[k]:
+                core.append((i, *struct.unpack_from("<iiiBBHHHiiii", rec, 0)))
+                body.append(np.frombuffer(rec, np.uint8, len(rec) - 36, 36))
+                taken += len(rec)
+                k += 1
+        np.save(os.path.join(out_dir, f"{name}_summary{suffix}.npy"), np.array([n_rec, n_bytes], np.float64))
+        if core:
+            np.save(os.path.join(out_dir, f"{name}_core{suffix}.npy"), np.array(core, np.float64))
+            np.save(os.path.join(out_dir, f"{name}_bytes{suffix}.npy"), np.concatenate(body).astype(np.float32))
+        log(f"dumped {name}: {len(core)} of {n_rec} records, {taken} bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -395,6 +502,12 @@ def main():
                          "per-GPU shards of C3 / C4 / C5 reported for coverage")
     ap.add_argument("--families", type=int, default=None, help="families per GPU (C2: 312,500)")
     ap.add_argument("--seed", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline value does not need: the device-resident roofline passes, "
+                         "the CPU baselines (see --no-cpu) and the level-6 input passes (see --level6-passes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed CLI pass wrote as DIR/<name>.npy "
+                         "(dump_outputs: record counts and a fixed sample of records of the three output BAMs)")
     ap.add_argument("--cpu-reps", type=int, default=2, help="passes of the CPU baseline over the batch")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--kernel-only", action="store_true", help="skip the whole-node CLI runs")
@@ -414,6 +527,8 @@ def main():
                          "subfamilies).  Below a config's subfamily sizes the CLI downsamples (random.seed(4)); "
                          "the device-resident batch is then capped at the same size")
     args = ap.parse_args()
+    if args.dump_outputs and (args.kernel_only or args.steps < 1):
+        ap.error("--dump-outputs writes the last timed CLI pass's outputs: it needs --steps >= 1 and no --kernel-only")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -455,8 +570,10 @@ def main():
     params_args = ["--max_reads", str(max_reads)] if max_reads != 100 else []
 
     # -- SSCS kernel roofline: device-resident passes ------------------------------
-    kavg, dev_bases, n_bad, dev_step = device_resident(packed, params, local, args.kernel_steps, 2)
-    log(f"[rank {rank}] device-resident step {dev_step * 1e3:.2f} ms")
+    kavg, dev_bases, n_bad, dev_step = None, 0, 0, None
+    if args.full or args.kernel_only:
+        kavg, dev_bases, n_bad, dev_step = device_resident(packed, params, local, args.kernel_steps, 2)
+        log(f"[rank {rank}] device-resident step {dev_step * 1e3:.2f} ms")
 
     # -- whole node: the CLI over a BAM of the same families -------------------------
     workdir = None
@@ -495,7 +612,12 @@ def main():
                 tdist.barrier()
             log(f"[rank {rank}] {args.steps} CLI passes in {e2e_s:.2f} s: "
                 f"{ {k: v for k, v in stats.items() if k != 'ranks'} }")
-            if not args.no_cpu and not dist and not args.sharded:
+            if args.dump_outputs and (rank == 0 or not args.sharded):
+                t0 = time.perf_counter()
+                dump_outputs(args.dump_outputs, os.path.join(workdir, f"cons{args.warmup + args.steps - 1}.bam"),
+                             suffix=f"_rank{rank}" if dist and not args.sharded else "")
+                log(f"[rank {rank}] --dump-outputs {args.dump_outputs} in {time.perf_counter() - t0:.1f} s")
+            if args.full and not args.no_cpu and not dist and not args.sharded:
                 quota, ncpu = cpu_cores()
                 threads = int(quota) if quota else min(16, ncpu or 1)
                 v, dt, st = cpu_baseline_whole_node(bam_path, params_args, workdir, args.cpu_reps, threads)
@@ -503,7 +625,7 @@ def main():
                              "host_cpus": ncpu, "consensus_bases": st.get("consensus_bases")}
                 log(f"[rank {rank}] CPU whole node (oracle backend, host codecs): {v / 1e6:.1f} M consensus "
                     f"bases/s, {dt:.2f} s per pass")
-            if args.level6_passes > 0 and not dist and not args.sharded and args.in_level != 6:
+            if args.full and args.level6_passes > 0 and not dist and not args.sharded and args.in_level != 6:
                 # the same families from a level-6 input (a BAM as aligners
                 # write it): more inflate work per byte, not the headline
                 bam6 = os.path.join(workdir, "in6.bam")
@@ -528,7 +650,7 @@ def main():
         in_bases = 0            # one input: rank 0's batch
     # per-rank busy time of the last CLI pass (whole pass, ingest thread, waits on the device)
     mine = {"rank": rank, "e2e_s_per_pass": (e2e_s or 0.0) / max(args.steps, 1),
-            "device_resident_ms": dev_step * 1e3,
+            "device_resident_ms": dev_step * 1e3 if dev_step is not None else None,
             **{k: round(v, 4) for k, v in stats.items()
                if k in ("ingest_s", "wait_s", "idle_s", "write_s", "run_s", "merge_s", "shard_rounds",
                         "consensus_bases")}}
@@ -538,29 +660,44 @@ def main():
         tdist.all_gather_object(per_rank, mine)
     if dist:
         slowest = shard.max_over_ranks(e2e_s or 0.0, device=red_dev)
-        dev_slowest = shard.max_over_ranks(dev_step, device=red_dev)
+        dev_slowest = shard.max_over_ranks(dev_step, device=red_dev) if dev_step is not None else None
         e2e_bases, in_bases, dev_bases, n_bad = shard.sum_over_ranks([e2e_bases, in_bases, dev_bases, n_bad],
                                                                      device=red_dev)
     else:
         slowest, dev_slowest = e2e_s or 0.0, dev_step
 
     if rank == 0:
-        alg = sscs_algorithmic_bytes(packed)
-        alg_padded = sscs_algorithmic_bytes(packed, padded=True)
-        if args.config == "C2":
-            dom, dom_label = "k_consensus_fast<ss>", ("k_consensus_fast<false, false> + k_fast_rows (single-strand "
-                                                      "consensus; the HIP-event slot spans both launches)")
-            dom_ms = kavg[dom]
-            # the slot's two launches: the kernel and its row expansion
-            traffic, tsrc = load_traffic("k_consensus_fast<false, false>", packed.n_fam)
-            rows_traffic, _ = load_traffic("k_fast_rows", packed.n_fam)
-            if traffic is not None and rows_traffic is not None:
-                traffic += rows_traffic
-        else:
-            dom_label = "single-strand stage (k_recmeta<ss> + k_consensus_fast<ss> + k_consensus_exact<ss> + k_consensus_general<ss>)"
-            dom_ms = sum(kavg[k] for k in _lib.KERNELS[0:4])
-            traffic, tsrc = None, None
-        achieved = alg / (dom_ms / 1000.0) / 1e9
+        roofline = dev_res = ss_gbps = None
+        if kavg is not None:                # the device-resident passes ran (--full, --kernel-only)
+            alg = sscs_algorithmic_bytes(packed)
+            alg_padded = sscs_algorithmic_bytes(packed, padded=True)
+            if args.config == "C2":
+                dom, dom_label = "k_consensus_fast<ss>", ("k_consensus_fast<false, false> + k_fast_rows (single-strand "
+                                                          "consensus; the HIP-event slot spans both launches)")
+                dom_ms = kavg[dom]
+                # the slot's two launches: the kernel and its row expansion
+                traffic, tsrc = load_traffic("k_consensus_fast<false, false>", packed.n_fam)
+                rows_traffic, _ = load_traffic("k_fast_rows", packed.n_fam)
+                if traffic is not None and rows_traffic is not None:
+                    traffic += rows_traffic
+            else:
+                dom_label = "single-strand stage (k_recmeta<ss> + k_consensus_fast<ss> + k_consensus_exact<ss> + k_consensus_general<ss>)"
+                dom_ms = sum(kavg[k] for k in _lib.KERNELS[0:4])
+                traffic, tsrc = None, None
+            achieved = alg / (dom_ms / 1000.0) / 1e9
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                        "kernel": dom_label,
+                        "kernel_ms": dom_ms, "algorithmic_bytes_per_launch": alg,
+                        "algorithmic_T": "max(pos + len) - min(pos) per subfamily (SURVEY §8d)",
+                        "achieved_padded": alg_padded / (dom_ms / 1000.0) / 1e9,
+                        "frac_padded": alg_padded / (dom_ms / 1000.0) / 1e9 / HBM_PEAK_GBS,
+                        "algorithmic_bytes_per_launch_padded": alg_padded,
+                        "traffic_source": (f"profiles/traffic.json ({tsrc.get('source', '')})" if tsrc else None)}
+            dev_res = {"consensus_bases_per_s": dev_bases / dev_slowest,
+                       "ms_per_step": dev_slowest * 1e3, "kernel_ms": kavg,
+                       "records_not_ok": n_bad}
+            ss_gbps = alg / (sum(kavg[k] for k in _lib.KERNELS[0:4]) / 1e3) / 1e9
         if args.kernel_only:
             value, ms_step = dev_bases / dev_slowest, dev_slowest * 1e3
             value_kind = "device-resident kernels only (--kernel-only)"
@@ -589,26 +726,16 @@ def main():
                        "input_bases_per_s": (in_bases / slowest) if slowest else None,
                        "consensus_records_per_pass": stats.get("consensus_records"),
                        "stages_s_last_pass": stage,
-                       "device_resident": {"consensus_bases_per_s": dev_bases / dev_slowest,
-                                           "ms_per_step": dev_slowest * 1e3, "kernel_ms": kavg,
-                                           "records_not_ok": n_bad},
-                       "single_strand_stage_GBps": alg / (sum(kavg[k] for k in _lib.KERNELS[0:4]) / 1e3) / 1e9,
+                       "device_resident": dev_res,
+                       "single_strand_stage_GBps": ss_gbps,
                        "parallelism": (f"one input sharded x{world} by ranges of whole families (cli --gpus {world}), "
                                        "one process per GPU, parallel part merge, no data-path collective"
                                        if args.sharded else
                                        f"family-sharded x{world}, one process per GPU, no data-path collective"),
                        "per_rank": per_rank, "shared_stream": shared},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": dom_label,
-                         "kernel_ms": dom_ms, "algorithmic_bytes_per_launch": alg,
-                         "algorithmic_T": "max(pos + len) - min(pos) per subfamily (SURVEY §8d)",
-                         "achieved_padded": alg_padded / (dom_ms / 1000.0) / 1e9,
-                         "frac_padded": alg_padded / (dom_ms / 1000.0) / 1e9 / HBM_PEAK_GBS,
-                         "algorithmic_bytes_per_launch_padded": alg_padded,
-                         "traffic_source": (f"profiles/traffic.json ({tsrc.get('source', '')})" if tsrc else None)},
+            "roofline": roofline,
         }
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             ko = cpu_baseline(packed, args.cpu_reps)
             if cpu_whole is not None:
                 # like for like with value: the whole CLI pass on the CPU

@@ -56,19 +56,19 @@ def test_library_is_gfx950_code_object():
     assert b"amdgcn-amd-amdhsa--gfx950" in data      # offload bundle target id
 
 
-def _c_sizeof(expr):
+def _c_sizeof(expr, tmp):
     src = f'#include "{HEADER}"\n#include <stdio.h>\n#include <stddef.h>\nint main(void){{printf("%zu\\n", (size_t)({expr}));return 0;}}\n'
-    exe = "/tmp/_dcr_sizeof"
+    exe = str(tmp / "dcr_sizeof")
     subprocess.run(["gcc", "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
     return int(subprocess.run([exe], capture_output=True, text=True, check=True).stdout)
 
 
-def test_ctypes_layouts_match_header():
+def test_ctypes_layouts_match_header(tmp_path):
     from duplexumiconsensusreads_amd.batch import DcrBatch, DcrOut, DcrReadInfo
     from duplexumiconsensusreads_amd.params import DcrParams
-    assert ctypes.sizeof(DcrParams) == _c_sizeof("sizeof(dcr_params)")
-    assert ctypes.sizeof(DcrBatch) == _c_sizeof("sizeof(dcr_batch)")
-    assert ctypes.sizeof(DcrOut) == _c_sizeof("sizeof(dcr_out)")
-    assert ctypes.sizeof(DcrReadInfo) == _c_sizeof("sizeof(dcr_read_info)")
-    assert DcrParams.qthresh.offset == _c_sizeof("offsetof(dcr_params, qthresh)")
-    assert DcrBatch.sub_off.offset == _c_sizeof("offsetof(dcr_batch, sub_off)")
+    assert ctypes.sizeof(DcrParams) == _c_sizeof("sizeof(dcr_params)", tmp_path)
+    assert ctypes.sizeof(DcrBatch) == _c_sizeof("sizeof(dcr_batch)", tmp_path)
+    assert ctypes.sizeof(DcrOut) == _c_sizeof("sizeof(dcr_out)", tmp_path)
+    assert ctypes.sizeof(DcrReadInfo) == _c_sizeof("sizeof(dcr_read_info)", tmp_path)
+    assert DcrParams.qthresh.offset == _c_sizeof("offsetof(dcr_params, qthresh)", tmp_path)
+    assert DcrBatch.sub_off.offset == _c_sizeof("offsetof(dcr_batch, sub_off)", tmp_path)

@@ -39,11 +39,11 @@ def test_library_exports_every_header_function():
         assert hasattr(lib, n), n
 
 
-def test_host_batch_layout_matches_header():
+def test_host_batch_layout_matches_header(tmp_path):
     src = (f'#include "{HEADER}"\n#include <stdio.h>\n#include <stddef.h>\n'
            'int main(void){printf("%zu %zu %zu %zu\\n", sizeof(dcr_host_batch), offsetof(dcr_host_batch, n_fam),'
            ' offsetof(dcr_host_batch, err_msg), sizeof(dcr_ingest_cfg));return 0;}\n')
-    exe = "/tmp/_dcr_io_sizeof"
+    exe = str(tmp_path / "dcr_io_sizeof")
     subprocess.run(["gcc", "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
     got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
     S = native_io.HostBatchStruct

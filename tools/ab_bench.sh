@@ -18,7 +18,7 @@ for r in $(seq 1 "$REPS"); do
     else
       set_env="${AB_VAR:-DCR_LIB}=duplexumiconsensusreads_amd/$lib"
     fi
-    env "$set_env" timeout -k 10 300 python3 -u bench.py --no-cpu --steps "$STEPS" --warmup 2 > "$f.txt" 2>&1 || { echo "bench $lib failed rc=$?"; tail -20 "$f.txt"; exit 1; }
+    env "$set_env" timeout -k 10 300 python3 -u bench.py --full --no-cpu --steps "$STEPS" --warmup 2 > "$f.txt" 2>&1 || { echo "bench $lib failed rc=$?"; tail -20 "$f.txt"; exit 1; }
     grep '^{' "$f.txt" | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); s=d['config']['stages_s_last_pass']; print('$lib', round(d['value']/1e6,1), 'M', 'l6', round(d['config']['whole_node_level6_input']['value']/1e6,1), 'ingest', s['ingest_s'], 'wait', s['wait_s'], 'idle', s['idle_s'], 'inflate_ms', round(s['gpu_inflate']['kernel_ms_per_pass'],1), 'host_cpu_s', s.get('host_cpu_s_per_pass'))" | tee -a "$O/ab.txt"
   done
 done

@@ -9,11 +9,13 @@
 # STEP:
 #   pytest[=EXPR]          pytest -m gpu (optionally -k EXPR)
 #   smoke                  __graft_entry__.smoke()
-#   bench[=ARGS]           python bench.py ARGS (default: the driver's default line) -> bench.json
+#   bench[=ARGS]           python bench.py ARGS (default: the plain headline run; --full adds the roofline,
+#                          CPU-baseline and level-6 legs) -> bench.json
 #   kbench=CONFIG          bench.py --config CONFIG --kernel-only --no-cpu -> bench_CONFIG.json
 #   ablate=CONFIG:NFAM:LIBS  tools/ablate.py (LIBS comma-separated libdcr_*.so names), outputs checked
 #   stamps=CONFIG:LIB      tools/stamps.py with a DCR_STAMP build
-#   kt=ARGS                rocprofv3 --kernel-trace --stats over bench.py ARGS -> kt/, kernel_grid.csv
+#   kt=ARGS                rocprofv3 --kernel-trace --stats over bench.py ARGS (--full for the roofline's
+#                          device-resident launches) -> kt/, kernel_grid.csv
 #   traffic                FETCH_SIZE / WRITE_SIZE passes over the C2 kernel bench -> traffic.json
 #   pmc=COUNTERS:LIB       one rocprofv3 --pmc pass over tools/ablate.py on LIB (C2)
 #   inflate=NMEM           tools/inflate_speed.py

@@ -1,6 +1,6 @@
 """Per-launch-shape kernel durations from a rocprofv3 kernel trace.
 
-rocprofv3 --stats averages every launch of a kernel together; bench.py
+rocprofv3 --stats averages every launch of a kernel together; bench.py --full
 launches the single-strand kernel both on the full device-resident batch
 (the roofline's launches) and on the CLI's smaller batches.  This groups the
 trace by (kernel, grid size) so the roofline launch's average can be read
