@@ -546,8 +546,7 @@ int dcr_run_batch(dcr_ctx *c, const dcr_batch *in, dcr_out *ss, dcr_out *ds) {
             hipLaunchKernelGGL((dcr::k_consensus_fast<true, true>), dim3(gx), dim3(dcr::kFastBlock), 0, c->stream, fa);
             HIP_TRY(hipEventRecord(ev[2], c->stream));
             hipLaunchKernelGGL(dcr::k_decide<true>, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
-            if (DCR_LAYOUT_KERNEL)
-                hipLaunchKernelGGL(dcr::k_ins_layout<true>, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
+            hipLaunchKernelGGL(dcr::k_ins_layout<true>, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
             hipLaunchKernelGGL(dcr::k_consensus_general<true>, dim3(grid_for(a.n_rec, 1024)), dim3(256), 0,
                                c->stream, a);
         } else {
@@ -570,8 +569,7 @@ int dcr_run_batch(dcr_ctx *c, const dcr_batch *in, dcr_out *ss, dcr_out *ds) {
                                    a);
             // after k_decide_deep: it reads the general list's entries, which
             // k_ins_layout marks decided (bit 31) for the records it decides
-            if (DCR_LAYOUT_KERNEL)
-                hipLaunchKernelGGL(dcr::k_ins_layout<false>, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
+            hipLaunchKernelGGL(dcr::k_ins_layout<false>, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
             hipLaunchKernelGGL(dcr::k_consensus_general<false>, dim3(grid_for(a.n_rec, 1024)), dim3(256), 0,
                                c->stream, a);
         }
@@ -983,7 +981,7 @@ int dcr_submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *
     }
     int64_t *bsz = (int64_t *)(wb + o_bsz);
     dcrw::DflArgs D{A.stream, A.rec_off + 2 * F, (uint8_t *)(wb + o_slots), bsz, (uint32_t *)(wb + o_tok), nullptr,
-                    DFL_CLAIM ? (unsigned long long *)(bsz + nbm + 1) : nullptr};
+                    (unsigned long long *)(bsz + nbm + 1)};
     hipLaunchKernelGGL(dcrw::k_deflate, dim3(gd), dim3(dfl::kT), sizeof(dfl::Shared), c->stream, D);
     HIP_TRY(hipGetLastError());
     int64_t *boff = (int64_t *)(wb + o_boff);

@@ -70,24 +70,6 @@ constexpr uint32_t kMaxIn = DFL_MAXIN;    // input bytes per BGZF block
 #ifndef DFL_HB
 #define DFL_HB 11
 #endif
-#ifndef DFL_CRCS
-#define DFL_CRCS 8                         // device CRC32 slice-by-N from LDS tables, N = 4 or 8 (0: bit by bit)
-#endif
-#ifndef DFL_SPEC
-#define DFL_SPEC 1                         // device parse: batched table warm-up, p + 1 preloaded (parse_dev)
-#endif
-#ifndef DFL_P1W
-#define DFL_P1W 1                          // device block hash: one dword load per four positions
-#endif
-#ifndef DFL_CODES_EARLY
-#define DFL_CODES_EARLY 1                  // device: literal / distance codes on waves 1-3 during the header
-#endif
-#ifndef DFL_CRC_LATE
-#define DFL_CRC_LATE 1                     // device: sub-block CRCs on the waves the code-length phase leaves idle
-#endif
-#ifndef DFL_XQ
-#define DFL_XQ 1                           // device match extension: one candidate queue per lane (0: candidate by candidate)
-#endif
 constexpr int kHB = DFL_HB;
 constexpr int kHN = 1 << kHB;
 constexpr uint32_t kNone = 0xffffffffu;
@@ -109,9 +91,7 @@ struct alignas(16) Shared {
         };
         uint32_t stage[(3 * kHN * 4 + kT * 2 * kLS * 2) / 4];   // P5: the compressed member (after P2)
     };
-#if DFL_CRCS
-    uint32_t crc_t[DFL_CRCS][256];        // slice-by-N CRC32 tables, filled once per workgroup (k_deflate)
-#endif
+    uint32_t crc_t[8][256];               // slice-by-8 CRC32 tables, filled once per workgroup (k_deflate)
     uint32_t lit_freq[288], dist_freq[32];
     uint8_t lit_len[288], dist_len[32], cl_len[19];
     uint16_t lit_code[288], dist_code[32], cl_code[19];   // bit-reversed (LSB-first) codes
@@ -333,7 +313,7 @@ DFL_HD inline uint32_t cand_at(uint32_t i, uint32_t c0, uint32_t c1, uint32_t c2
 // four bytes compared together (one LDS round trip each), so a literal costs
 // three round trips; only candidates that match >= 4 bytes are extended, in
 // candidate order, skipping any that cannot beat the best so far.
-#if DFL_DEVICE && DFL_SPEC
+#if DFL_DEVICE
 // The device parse: the same decisions as parse() below, scheduled for
 // fewer dependent LDS round trips per lane.
 //  - The recency table is warmed 8 positions per round trip: the 8 sets'
@@ -355,11 +335,7 @@ DFL_UNROLL
     for (int i = 0; i < kLS; ++i) t32[i] = 0;
     {
         const uint32_t S = hi - lo;
-#ifdef DFL_ABL_NOWARM                      // ablation: no table warm-up
-        for (uint32_t qb = lo; qb < lo; qb += 8) {
-#else
         for (uint32_t qb = lo >= S ? lo - S : 0; qb < lo; qb += 8) {
-#endif
             const uint32_t di = qb >> 2, o = qb & 3;
             const uint32_t D0 = wi[di], D1 = wi[di + 1], D2 = wi[di + 2], D3 = wi[di + 3];
             const uint32_t E[3] = {__builtin_amdgcn_alignbyte(D1, D0, o), __builtin_amdgcn_alignbyte(D2, D1, o),
@@ -511,7 +487,7 @@ DFL_UNROLL
 
 template <class V>
 DFL_HD inline void parse(Shared &s, uint32_t n, int lane, uint32_t lo, uint32_t hi, V &v) {
-#if DFL_DEVICE && DFL_SPEC
+#if DFL_DEVICE
     parse_dev(s, n, lane, lo, hi, v);
     return;
 #endif
@@ -574,7 +550,7 @@ DFL_UNROLL
 #endif
                 if (p >= (uint32_t)k && vk == vp) ok |= 1u << (3 + k);
             }
-#if DFL_DEVICE && DFL_XQ
+#if DFL_DEVICE
             // The candidates with >= 4 matching bytes are extended through one
             // queue per lane: each iteration is one kMW-dword step of the
             // lane's current candidate, so a wave runs as many iterations as
@@ -650,16 +626,6 @@ DFL_UNROLL
 struct CountV {            // P2: symbol histogram, extra bits
     Shared &s;
     uint32_t extra = 0;
-#ifdef DFL_ABL_NOCNT                       // ablation (invalid members): the histogram atomics spread over bins
-    int lane;
-    DFL_HD void lit(uint8_t b) { aadd(&s.lit_freq[(b + (uint32_t)lane) & 255], 1); }
-    DFL_HD void match(uint32_t len, uint32_t d) {
-        const Sym L = len_code(len), D = dist_code(d);
-        aadd(&s.lit_freq[257 + (L.sym + (uint32_t)lane) % 29], 1);
-        aadd(&s.dist_freq[(D.sym + (uint32_t)lane) % 30], 1);
-        extra += L.nb + D.nb;
-    }
-#else
     DFL_HD void lit(uint8_t b) { aadd(&s.lit_freq[b], 1); }
     DFL_HD void match(uint32_t len, uint32_t d) {
         const Sym L = len_code(len), D = dist_code(d);
@@ -667,7 +633,6 @@ struct CountV {            // P2: symbol histogram, extra bits
         aadd(&s.dist_freq[D.sym], 1);
         extra += L.nb + D.nb;
     }
-#endif
 };
 
 struct TokV {              // P2: the lane's tokens (kTokE layout)
@@ -691,13 +656,9 @@ struct CountTokV {         // P2: both
 };
 
 // the tokens of a lane again, from the token buffer
-#ifndef DFL_TOKPF
-#define DFL_TOKPF 4                        // token entries in flight during a replay (1 or 4)
-#endif
 template <class V>
 DFL_HD inline void replay(const Shared &s, const uint32_t *t, int lane, uint32_t lo, V &v) {
     uint32_t p = lo;
-#if DFL_TOKPF == 4
     // four entries in flight (the token buffer is in HBM / L2): a ring
     // shifted by one per entry (entries past the tail hold stale words,
     // never used)
@@ -708,14 +669,6 @@ DFL_HD inline void replay(const Shared &s, const uint32_t *t, int lane, uint32_t
         x2 = x3;
         x3 = x4;
         if (e + 4 < kTokE) x4 = t[(e + 4) * kT + lane];
-#else
-    uint32_t xn = t[lane];
-    for (int e = 0; e < kTokE; ++e) {
-        // the next entry's load is in flight while this one is replayed
-        // (entries past the tail hold stale words, never used)
-        const uint32_t x = xn;
-        if (e + 1 < kTokE) xn = t[(e + 1) * kT + lane];
-#endif
         const uint32_t run = (x >> 23) & 255;
         v.lits(p, run);
         p += run;
@@ -871,27 +824,15 @@ struct EmitV {             // P5: write a lane's tokens
 };
 
 // ---- Huffman code lengths (one wave) ----------------------------------------------
-// The serial code below runs on one lane.  DFL_SERIAL_WAVE=1 runs it on a
-// whole wave with the same data in every lane instead: each LDS read goes
-// through DFL_U() (readfirstlane), so indices and loop bounds live in scalar
-// registers and the branches are scalar; every lane stores the same value to
-// the same address.  That measured slower (readfirstlane after each LDS
-// load), so one lane it is.  The host emulation runs it once (lane 0).
-#ifndef DFL_SERIAL_WAVE
-#define DFL_SERIAL_WAVE 0      // 1: a whole wave with readfirstlane reads (measured slower: 6.95 vs 6.56 ms)
-#endif
-#if DFL_DEVICE && DFL_SERIAL_WAVE
-#define DFL_U(x) __builtin_amdgcn_readfirstlane((uint32_t)(x))
-#else
+// The serial code below runs on one lane.  Running it on a whole wave with
+// the same data in every lane instead (each LDS read through a readfirstlane
+// in DFL_U(), so indices, loop bounds and branches are scalar) measured
+// slower (6.95 vs 6.56 ms: a readfirstlane after each LDS load), so one lane
+// it is.  The host emulation runs it once (lane 0).
 #define DFL_U(x) ((uint32_t)(x))
-#endif
-// the wave that runs a serial step: the device's whole wave of `lane0`, the host's lane0 itself
+// the lane that runs a serial step
 DFL_HD inline bool serial_lane(int lane, int lane0) {
-#if DFL_DEVICE && DFL_SERIAL_WAVE
-    return (lane >> 6) == (lane0 >> 6);
-#else
     return lane == lane0;
-#endif
 }
 // In-place minimum-redundancy code lengths (Moffat & Katajainen 1995) over
 // a[0..m) = frequencies sorted ascending; on return a[i] is the code length
@@ -1341,7 +1282,7 @@ DFL_HD inline void p0_clear(Shared &s, int lane) {
 DFL_HD inline void p1_hash(Shared &s, uint32_t n, int lane) {
     uint32_t lo, hi;
     lane_range(n, lane, lo, hi);
-#if DFL_DEVICE && DFL_P1W
+#if DFL_DEVICE
     // a dword at a time: each input dword loaded once (the next one ahead),
     // its four positions' bytes by funnel shifts
     {
@@ -1376,42 +1317,32 @@ DFL_HD inline uint32_t sub_crc(const Shared &s, uint32_t n, int l);
 DFL_HD inline void p2_count(Shared &s, uint32_t n, int lane, uint32_t *tok) {
     uint32_t lo, hi;
     lane_range(n, lane, lo, hi);
-#ifdef DFL_ABL_NOCNT
-    CountTokV v{CountV{s, 0, lane}, TokV{tok, lane}};
-#else
     CountTokV v{CountV{s}, TokV{tok, lane}};
-#endif
     parse(s, n, lane, lo, hi, v);
     v.t.finish();
     if (v.c.extra) aadd(&s.extra_bits, v.c.extra);
-#if !(DFL_DEVICE && DFL_CRC_LATE)
+#if !DFL_DEVICE
     s.lane_crc[lane] = sub_crc(s, n, lane);
 #endif
 }
 
 // CRC32 register of sub-block l (no init / final xor), shifted past the rest
 // of the block.  On the device it runs during the code-length phase, on the
-// two waves that phase leaves idle (k_deflate, DFL_CRC_LATE).
+// two waves that phase leaves idle (k_deflate).
 DFL_HD inline uint32_t sub_crc(const Shared &s, uint32_t n, int l) {
     uint32_t lo, hi;
     lane_range(n, l, lo, hi);
     uint32_t c = 0;
-#if defined(DFL_ABL_NOCRC)
-    (void)c;
-#elif DFL_DEVICE && DFL_CRCS
-    // slice-by-N: N independent table loads per N / 4 dwords
+#if DFL_DEVICE
+    // slice-by-8: 8 independent table loads per 2 dwords
     uint32_t p = lo;
     for (; p < hi && (p & 3); ++p) c = s.crc_t[0][(c ^ s.in[p]) & 0xff] ^ (c >> 8);
     const uint32_t *wi = reinterpret_cast<const uint32_t *>(s.in);
-    for (; p + DFL_CRCS <= hi; p += DFL_CRCS) {
+    for (; p + 8 <= hi; p += 8) {
         const uint32_t a = c ^ wi[p >> 2];
-#if DFL_CRCS == 8
         const uint32_t b = wi[(p >> 2) + 1];
         c = s.crc_t[7][a & 255] ^ s.crc_t[6][(a >> 8) & 255] ^ s.crc_t[5][(a >> 16) & 255] ^ s.crc_t[4][a >> 24] ^
             s.crc_t[3][b & 255] ^ s.crc_t[2][(b >> 8) & 255] ^ s.crc_t[1][(b >> 16) & 255] ^ s.crc_t[0][b >> 24];
-#else
-        c = s.crc_t[3][a & 255] ^ s.crc_t[2][(a >> 8) & 255] ^ s.crc_t[1][(a >> 16) & 255] ^ s.crc_t[0][a >> 24];
-#endif
     }
     for (; p < hi; ++p) c = s.crc_t[0][(c ^ s.in[p]) & 0xff] ^ (c >> 8);
 #else

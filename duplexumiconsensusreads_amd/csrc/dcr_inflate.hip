@@ -26,7 +26,6 @@
 //     zlib's crc32_combine algebra, dcr_deflate.h multmodp);
 //   - ISIZE and CRC32 checked against the member trailer on the device.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include <condition_variable>
 #include <cstring>
@@ -74,9 +73,6 @@ struct IStamp {
 // (35.2 -> 47.5 GB/s over all members in one launch; profiles/r04e)
 #ifndef DINF_WG_PER_CU
 #define DINF_WG_PER_CU 16 // k_inflate launch grid cap per CU (0: one workgroup per member)
-#endif
-#ifndef DINF_CU_SHARE
-#define DINF_CU_SHARE 0   // diagnostic builds: the streaming inflate on DINF_CU_SHARE of every 8 CUs (0: all)
 #endif
 #ifndef DINF_RING
 #define DINF_RING 4096    // LDS output history per member (bytes)
@@ -717,7 +713,7 @@ dcr_inflater *dcr_inflater_create(int device) {
     }
     h->base.x8n_piece = dfl::x8nmodp(dinf::kPiece);
     h->n_cu = std::max(1, prop.multiProcessorCount);
-    if (DINF_WG_PER_CU > 0) h->grid_cap = DINF_WG_PER_CU * h->n_cu * (DINF_CU_SHARE > 0 ? DINF_CU_SHARE : 8) / 8;
+    if (DINF_WG_PER_CU > 0) h->grid_cap = DINF_WG_PER_CU * h->n_cu;
     return h;
 }
 
@@ -954,14 +950,7 @@ extern "C" dcr_inflate_stream *dcr_inflate_stream_open(dcr_inflater *h, const ui
     }
     InflSlots &S = *h->slots;
     (void)hipSetDevice(h->device);
-    auto make_k = [&]() {
-        if (DINF_CU_SHARE <= 0) return hipStreamCreateWithFlags(&S.s_k, hipStreamNonBlocking);
-        std::vector<uint32_t> mask((size_t)(h->n_cu + 31) / 32, 0u);
-        for (int i = 0; i < h->n_cu; ++i)
-            if (i % 8 < DINF_CU_SHARE) mask[(size_t)i / 32] |= 1u << (i % 32);
-        return hipExtStreamCreateWithCUMask(&S.s_k, (uint32_t)mask.size(), mask.data());
-    };
-    if ((!S.s_k && make_k() != hipSuccess) ||
+    if ((!S.s_k && hipStreamCreateWithFlags(&S.s_k, hipStreamNonBlocking) != hipSuccess) ||
         (!S.s_out && hipStreamCreateWithFlags(&S.s_out, hipStreamNonBlocking) != hipSuccess)) {
         std::lock_guard<std::mutex> g(h->mu);
         S.busy = false;

@@ -37,10 +37,6 @@ struct RecMeta {
 };
 static_assert(sizeof(RecMeta) == 32, "RecMeta is one s_load_dwordx8");
 
-#ifndef DCR_LAYOUT_KERNEL
-#define DCR_LAYOUT_KERNEL 1   // insertion layouts by events in k_ins_layout (0: the general kernel steps columns)
-#endif
-
 struct Workspace {
     dcr_read_info *info;    // [n_reads]
     uint32_t *norm_cig;     // [n_cigar] normalised runs (M/I/D)

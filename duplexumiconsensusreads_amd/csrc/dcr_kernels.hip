@@ -38,14 +38,8 @@
 #ifndef DCR_GSTAMP
 #define DCR_GSTAMP 0  // diagnostic builds only (tools/gstamps.py): per-phase s_memtime cycles of the general kernel
 #endif
-#ifndef DCR_LAYHOIST
-#define DCR_LAYHOIST 1  // k_ins_layout: a record of <= 64 reads builds its read table once
-#endif
 #ifndef DCR_LAYU
 #define DCR_LAYU 2    // k_ins_layout: reads whose byte loads are in flight together (2: 5 waves per SIMD; 4: 4, slower)
-#endif
-#ifndef DCR_LAYCLAIM
-#define DCR_LAYCLAIM 1  // k_ins_layout: records claimed one at a time past the first (0: fixed stride)
 #endif
 #ifndef DCR_LAYOCC
 #define DCR_LAYOCC 1  // k_ins_layout: waves per SIMD its launch bounds ask for
@@ -56,42 +50,17 @@
 #ifndef DCR_EXACT_OCC
 #define DCR_EXACT_OCC 4  // fast kernel (EXACT instantiation): waves per SIMD the launch bounds ask for
 #endif
-#ifndef DCR_TRIM2
-#define DCR_TRIM2 1   // fast kernel: the 3' trim of C2-shaped records checked from the evidence counts
-#endif
-#ifndef DCR_ROWS
-#define DCR_ROWS 1    // fast kernel: decided scalars as one 16-byte row per record, expanded by k_fast_rows
-#endif
-#ifndef DCR_DEFER
-#define DCR_DEFER 1   // fast kernel: a record's row stored after the next record's staging (its vmcnt(0) does not wait
-                      // for it; deferring the column stores too held registers across the loop and was slower)
-#endif
-#ifndef DCR_LCPOL
-#define DCR_LCPOL 0   // fast kernel: cache policy of the staging loads (gfx950 aux bits: 2 = nt)
-#endif
-#ifndef DCR_SCPOL
-#define DCR_SCPOL 0   // fast kernel: cache policy of the column stores
-#endif
-#ifndef DCR_VMPAD
-#define DCR_VMPAD 0   // fast kernel: range-checked-out stores after the prefetch (see the record loop)
-#endif
-#ifndef DCR_STRIDE
-#define DCR_STRIDE 1  // fast kernel: evenly spaced reads' codes addressed by a stepped VGPR (no per-read readlane)
-#endif
-#ifndef DCR_ST4
-#define DCR_ST4 0     // fast kernel (common instantiation): column stores four columns per lane through the free stage
-                      // (4 stores per record instead of 4 per tile: measured level, profiles/r06h)
+#ifndef DCR_GEN_OCC
+#define DCR_GEN_OCC 2    // general kernel: waves per SIMD the launch bounds ask for
 #endif
 #ifndef DCR_ABL
 #define DCR_ABL 0   // diagnostic builds only (tools/ablate.py); fast kernel: 1 staging only, 2 +products,
-                    // 4 always the exact pairwise mean, 5 no per-column stores, 6 every single-strand record
-                    // staged from the fast list's first record's bytes (cache-resident: the kernel without its
-                    // HBM reads), 7 column stores cache-resident (DCR_RSRC_*), 8 column stores at
-                    // 64-column-aligned offsets (records overlap: timing only)
+                    // 4 always the exact pairwise mean, 5 no per-column stores; general kernel: 1 staging only,
+                    // 2 +products, 3 +finalize, 9 without the > 64-read insertion layout, 10 without the
+                    // <= 64-read insertion layout, 11 without the records free of insertions, 12 without any
+                    // insertion layout
 #endif
 
-#define DCR_STR_(x) #x
-#define DCR_STR(x) DCR_STR_(x)
 namespace dcr {
 
 constexpr int kStageElems = 2048;        // per-wave LDS staging (16-bit codes)
@@ -1464,7 +1433,7 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
     // insertion records that k_ins_layout laid out: the tiles load their rows
     // (no column steps, flag pass or windows here)
     const int64_t lrec = (DUPLEX ? 4 * (int64_t)a.in.n_fam : 0) + rec;
-    const bool laid = DCR_LAYOUT_KERNEL && !FAST && ins && cols_lds && R <= kBigCh * kWave && a.ws.lay_base[lrec] > 0;
+    const bool laid = !FAST && ins && cols_lds && R <= kBigCh * kWave && a.ws.lay_base[lrec] > 0;
     uint64_t imask[4] = {0ull, 0ull, 0ull, 0ull};
     const uint16_t *lrows = nullptr;
     if (laid) {
@@ -2578,9 +2547,6 @@ static_assert(kWave0 % 16 == 0, "16-byte aligned stages");
 // table's unused half) and keeps its column words in the codes' space, dead
 // once the evidence is summed: 22,240 B per block, seven blocks (28 waves)
 // per CU.
-#ifndef DCR_LDS_PAD
-#define DCR_LDS_PAD 0
-#endif
 template <bool EXACT>
 struct Region {
     static constexpr int kCodes = EXACT ? 0x1000 : 0xC00;
@@ -2589,7 +2555,7 @@ struct Region {
     static constexpr int kList = kCodes + 1024;            // EXACT: u8 [256] the undecided columns, compacted
     static constexpr int kBytes = kCodes + 512 + (EXACT ? 512 + 256 : 0);
     static constexpr int kDw = kCodes / 2 / 4 / kWave;     // staged dwords per lane: 8 / 6
-    static constexpr int kLds = kWave0 + (EXACT ? kWaves : kWaves - 1) * kBytes + DCR_LDS_PAD;   // PAD: diagnostic builds
+    static constexpr int kLds = kWave0 + (EXACT ? kWaves : kWaves - 1) * kBytes;
     __device__ static constexpr int base(int wave) {       // wave's region
         return EXACT ? kWave0 + wave * kBytes : (wave == 0 ? kTable8 : kWave0 + (wave - 1) * kBytes);
     }
@@ -2627,7 +2593,6 @@ template <bool DUPLEX, int NDW>
 __device__ __forceinline__ void fast_load(const FastArgs &a, RecMeta m, const RecMeta *mlater, int lane,
                                           FastStage<NDW> &st) {
     const int ndw = (int)(m.w >> 15);
-    if (DCR_ABL == 6 && !DUPLEX) m.base_al = a.meta[0].base_al;   // diagnostic: cache-resident bytes
     // range: the array's last dword read whole (device allocations are padded
     // to at least 16 bytes, as the 16-byte-aligned staging already assumes)
     const int64_t left = ((a.nbytes + 3) & ~(int64_t)3) - m.base_al;
@@ -2639,12 +2604,11 @@ __device__ __forceinline__ void fast_load(const FastArgs &a, RecMeta m, const Re
 #pragma unroll
     for (int u = 0; u < NDW; ++u) {
         if (u * kWave < ndw) {
-            st.vb[u] = __builtin_amdgcn_raw_buffer_load_b32(rb, 4 * lane + 256 * u, 0, DCR_LCPOL);
-            st.vq[u] = __builtin_amdgcn_raw_buffer_load_b32(rq, 4 * lane + 256 * u, 0, DCR_LCPOL);
+            st.vb[u] = __builtin_amdgcn_raw_buffer_load_b32(rb, 4 * lane + 256 * u, 0, 0);
+            st.vq[u] = __builtin_amdgcn_raw_buffer_load_b32(rq, 4 * lane + 256 * u, 0, 0);
         }
     }
     const int R = (int)(m.w & 127u);
-    if (DCR_ABL == 6 && !DUPLEX) m.g0 = a.meta[0].g0;
     st.rm = a.rmeta[m.g0 + min(lane, R - 1)];
     st.mv = ((const uint32_t *)mlater)[lane & 7];
 }
@@ -2707,7 +2671,7 @@ __device__ __forceinline__ void run_evidence8(Evidence8<NT> &ev, const uint8_t *
                                               int lane) {
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt) ev.lo[tt] = ev.hi[tt] = 0u;
-    if (FULL && DCR_STRIDE) {
+    if (FULL) {
         // the reads' stage addresses evenly spaced (reads of one length packed
         // back to back: the C2 shape): a lane's code address is one VGPR
         // stepped by the stride, with no per-read readlane or scalar clamp.
@@ -3147,7 +3111,7 @@ __device__ __forceinline__ Staged trim_record(const FastArgs &a, const RecMeta &
         const int tl = lane < R ? (x >> 8) & 255 : 0;
         bool full = true;
         if (QUICK && !a.want_info && !any_bad) {
-            if (DCR_TRIM2 && __ballot(lane < R && (col != 0 || tl != s.T)) == 0) {
+            if (__ballot(lane < R && (col != 0 || tl != s.T)) == 0) {
                 // the first / last codes are only loaded here; finish_record
                 // reads them after the evidence, so no round trip is waited on
                 lds_fence();
@@ -3197,7 +3161,7 @@ __device__ __forceinline__ double div1000(int k) {
 // a status was written (nothing else to do)
 constexpr int kFinQueue = 0, kFinDone = 1, kFinStatus = 2;
 
-// a decided record's row (lanes 0-3), held until the next record is staged (DCR_DEFER)
+// a decided record's row (lanes 0-3), held until the next record is staged
 struct Pend {
     uint32_t v;
 };
@@ -3207,7 +3171,7 @@ __device__ __forceinline__ int finish_record(const FastArgs &a, const RecMeta &m
                                              const int stage_addr, const int ov_addr, const int rm_addr, const int list_addr,
                                              const int lane,
                                              Stamps &sp, const double2 *xt, const uint32_t *r1, const double *qt,
-                                             const int fi, Pend &pd) {
+                                             Pend &pd) {
     const int64_t rec = m.rec;
     const int64_t off = m.off;
     const int R = (int)(m.w & 127u);
@@ -3277,13 +3241,10 @@ __device__ __forceinline__ int finish_record(const FastArgs &a, const RecMeta &m
     // branching around them (no exec-mask branch in the loop over tiles)
     // (made where they are used, so their 16 scalar registers are not held
     // across the tile loop; unused in the EXACT instantiation)
-// (DCR_ABL 7, diagnostic: every record's columns stored over the first 4,096
-// columns of the arrays, cache-resident: the stores without their HBM traffic)
-#define DCR_OFF_ (DCR_ABL == 7 ? (off & 4095) : DCR_ABL == 8 ? (off & ~(int64_t)63) : off)
-#define DCR_RSRC_D __builtin_amdgcn_make_buffer_rsrc((void *)(a.O.d + DCR_OFF_), (short)0, 2 * T16, 0x00020000)
-#define DCR_RSRC_E __builtin_amdgcn_make_buffer_rsrc((void *)(a.O.e + DCR_OFF_), (short)0, 2 * T16, 0x00020000)
-#define DCR_RSRC_S __builtin_amdgcn_make_buffer_rsrc((void *)(a.O.seq + DCR_OFF_), (short)0, T16, 0x00020000)
-#define DCR_RSRC_Q __builtin_amdgcn_make_buffer_rsrc((void *)(a.O.qual + DCR_OFF_), (short)0, T16, 0x00020000)
+#define DCR_RSRC_D __builtin_amdgcn_make_buffer_rsrc((void *)(a.O.d + off), (short)0, 2 * T16, 0x00020000)
+#define DCR_RSRC_E __builtin_amdgcn_make_buffer_rsrc((void *)(a.O.e + off), (short)0, 2 * T16, 0x00020000)
+#define DCR_RSRC_S __builtin_amdgcn_make_buffer_rsrc((void *)(a.O.seq + off), (short)0, T16, 0x00020000)
+#define DCR_RSRC_Q __builtin_amdgcn_make_buffer_rsrc((void *)(a.O.qual + off), (short)0, T16, 0x00020000)
     // more reads than r_safe: L_b may underflow (fast_constants), no column is decided here
     const bool force = R > a.r_safe;
     int dmax = -1, dmin = 0x7fffffff;
@@ -3342,19 +3303,11 @@ __device__ __forceinline__ int finish_record(const FastArgs &a, const RecMeta &m
                 letter = t < T ? letter : 0x4Eu;
                 qv = t < T ? qv : 0u;
             }
-            if (DCR_ST4) {
-                // the column word (d | e << 6 | sel << 12, sel = the call or
-                // 4: 'N' / quality 0 past T) into the free stage; the stores
-                // go four columns per lane once the record is known decided
-                const uint32_t sel = tt == NT - 1 && t >= T ? 4u : kb;
-                *(uint16_t *)(ov + 2 * t) = (uint16_t)((uint32_t)d | ((uint32_t)e << 6) | (sel << 12));
-            } else {
             // the tile's offset as the scalar offset (no per-tile vector add)
-            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)d, DCR_RSRC_D, 2 * lane, 128 * tt, DCR_SCPOL);
-            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)e, DCR_RSRC_E, 2 * lane, 128 * tt, DCR_SCPOL);
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)letter, DCR_RSRC_S, lane, 64 * tt, DCR_SCPOL);
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)qv, DCR_RSRC_Q, lane, 64 * tt, DCR_SCPOL);
-            }
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)d, DCR_RSRC_D, 2 * lane, 128 * tt, 0);
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)e, DCR_RSRC_E, 2 * lane, 128 * tt, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)letter, DCR_RSRC_S, lane, 64 * tt, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)qv, DCR_RSRC_Q, lane, 64 * tt, 0);
         }
         fx += live ? __umul24((uint32_t)e, m720[d]) : 0u;
         dmax = max(dmax, live ? d : -1);
@@ -3369,27 +3322,6 @@ __device__ __forceinline__ int finish_record(const FastArgs &a, const RecMeta &m
     sp.mark(12);                         // [11] decision (of [5] finalize)
     const bool exact = __ballot(und) != 0;
     if (!EXACT && exact) return kFinQueue;
-    if (!EXACT && DCR_ST4 && DCR_ABL != 5) {
-        // d / e / seq / qual four columns per lane (8-, 8-, 4- and 4-byte
-        // stores): 4 store instructions per record instead of 4 per tile.
-        // The vector memory path pays per instruction (and per lane), not per
-        // byte: a C2 record's twelve 1- and 2-byte stores cost the kernel
-        // ~20 % (profiles/r06g), range-checked-out ones nothing.
-        lds_fence();
-        // lanes past the region (4 lane >= T16) are dropped by the resources' range checks
-        const uint2 w = *(const uint2 *)(ov + 8 * lane);
-        const uint32_t sel = ((w.x >> 12) & 7u) | ((w.x >> 20) & 0x700u) | ((w.y << 4) & 0x70000u) |
-                             ((w.y >> 4) & 0x7000000u);
-        const uint32_t letters = __builtin_amdgcn_perm(0x4Eu, 0x47435441u, sel);            // "ATCG"[call] or 'N'
-        const uint32_t quals = __builtin_amdgcn_perm(0u, (uint32_t)a.maxq * 0x01010101u, sel); // maxQ or 0
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        const v2i dv = {(int)(w.x & 0x003F003Fu), (int)(w.y & 0x003F003Fu)};
-        const v2i evv = {(int)((w.x >> 6) & 0x003F003Fu), (int)((w.y >> 6) & 0x003F003Fu)};
-        __builtin_amdgcn_raw_buffer_store_b64(dv, DCR_RSRC_D, 8 * lane, 0, DCR_SCPOL);
-        __builtin_amdgcn_raw_buffer_store_b64(evv, DCR_RSRC_E, 8 * lane, 0, DCR_SCPOL);
-        __builtin_amdgcn_raw_buffer_store_b32(letters, DCR_RSRC_S, 4 * lane, 0, DCR_SCPOL);
-        __builtin_amdgcn_raw_buffer_store_b32(quals, DCR_RSRC_Q, 4 * lane, 0, DCR_SCPOL);
-    }
     // exact columns' character | quality << 8, as u16 per column in the wave's
     // read-word LDS (free once the read words are in registers)
     uint16_t *chq = (uint16_t *)(lds + rm_addr);
@@ -3637,7 +3569,7 @@ __device__ __forceinline__ int finish_record(const FastArgs &a, const RecMeta &m
     bool slow = EXACT ? (R > 16 || DCR_ABL == 4) : false;
     if (!slow) {
         S = (uint32_t)wave_sum((int)(fx + (uint32_t)fxd));
-        if (EXACT || !DCR_ROWS) {
+        if (EXACT) {
             // the rational 25 S / (18018 T) in doubles: k = rint, remainder exact
             const int64_t num = 25 * (int64_t)S;
             const int den = 18018 * T;
@@ -3650,9 +3582,6 @@ __device__ __forceinline__ int finish_record(const FastArgs &a, const RecMeta &m
             const double Ed = div1000(k);
             E_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)__double_as_longlong(Ed));
             E_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)__double_as_longlong(Ed) >> 32));
-            // the common kernel kept no column words for the double walk: the
-            // EXACT kernel takes the record (a tie is rare)
-            if (!EXACT && slow) return kFinQueue;
         }
     }
     if (slow) {
@@ -3678,9 +3607,7 @@ __device__ __forceinline__ int finish_record(const FastArgs &a, const RecMeta &m
     if (__builtin_expect(__builtin_fabs(fr - 0.5) > 1e-9 * (1.0 + y), 1) && DCR_ABL != 4) {
         const double ky = __builtin_rint(y);
         E = ky >= 0.0 && ky <= 1000.0 ? div1000((int)ky) : ky / 1000.0;
-    } else if (!EXACT) {
-        return kFinQueue;                // near a half-integer: the EXACT pass walks numpy's pairwise sum
-    } else {
+    } else {                             // near a half-integer: numpy's pairwise sum
         lds_fence();
         double *et = (double *)(lds + stage_addr);
         const int ln = lane;
@@ -3702,7 +3629,7 @@ __device__ __forceinline__ int finish_record(const FastArgs &a, const RecMeta &m
     E_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)__double_as_longlong(E) >> 32));
     }
     sp.mark(9);                          // [8] mean
-    if (!EXACT && DCR_ROWS) {
+    if (!EXACT) {
         // the record's scalars as one 16-byte row at its fast-list index
         // (k_fast_rows expands it into the ten dcr_out arrays and rounds the
         // mean): pos (:790, first = 0 here), T | D << 8 | M << 16 | MAPQ << 24
@@ -3716,10 +3643,10 @@ __device__ __forceinline__ int finish_record(const FastArgs &a, const RecMeta &m
         v = write_lane<3>(v, 1u);
         // lanes 0-3 (a buffer store on the row's 16 bytes: the other lanes'
         // words fall outside it, no branch)
-        if (DCR_DEFER) pd.v = v;         // the caller stores it after the next record's staging
-        else
-            __builtin_amdgcn_raw_buffer_store_b32(v, __builtin_amdgcn_make_buffer_rsrc((void *)(a.rows + fi), (short)0, 16,
-                                                                                           0x00020000), 4 * lane, 0, 0);
+        // the caller stores it after the next record's staging (its vmcnt(0)
+        // does not wait for it; deferring the column stores too held registers
+        // across the loop and was slower)
+        pd.v = v;
         sp.mark(10);                     // [9] record scalars
         return kFinDone;
     }
@@ -3905,14 +3832,9 @@ __global__ __launch_bounds__(fk::kBlockThreads, EXACT ? DCR_EXACT_OCC : DCR_FAST
     // as a vector load (the descriptor load of the prefetch depends on it; a
     // scalar load issued there stalled the issue for its whole latency)
     int xv = EXACT ? a.xlist[opaque(nxt(i2))] : 0;
-    if (!EXACT && DCR_VMPAD > 0) {      // the same padding as after every later prefetch (the loop's entry path too)
-        const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void *)a.rows, (short)0, 0, 0x00020000);
-#pragma unroll
-        for (int k = 0; k < DCR_VMPAD; ++k) __builtin_amdgcn_raw_buffer_store_b32(0u, rz, 4 * lane0, 256 * k, 0);
-    }
     Stamps sp;
     int pend = 0, npend = 0;           // !EXACT: queued fast-list indices (lane p holds the p-th)
-    // DCR_DEFER: the last decided record's row, stored once the next record's
+    // the last decided record's row, stored once the next record's
     // bytes are staged: every VMEM store still in flight at a staging is
     // waited for there (loads and stores share vmcnt on gfx950, so the wait
     // for the prefetch is a vmcnt(0)), and the row was the record's last store
@@ -3920,7 +3842,7 @@ __global__ __launch_bounds__(fk::kBlockThreads, EXACT ? DCR_EXACT_OCC : DCR_FAST
     pd.v = 0;
     int row_i = -1;                    // the pending record's fast-list index (-1: none)
     auto store_row = [&](int ln) {
-        if (!EXACT && DCR_ROWS && DCR_DEFER && row_i >= 0) {
+        if (!EXACT && row_i >= 0) {
             __builtin_amdgcn_raw_buffer_store_b32(pd.v, __builtin_amdgcn_make_buffer_rsrc((void *)(a.rows + row_i), (short)0,
                                                                                           16, 0x00020000), 4 * ln, 0, 0);
             row_i = -1;
@@ -3939,34 +3861,6 @@ __global__ __launch_bounds__(fk::kBlockThreads, EXACT ? DCR_EXACT_OCC : DCR_FAST
         // lane-derived addresses are formed per record, not hoisted out of the
         // record loop into registers held across it
         const int lane = opaque(lane0);
-#if defined(DCR_PADV) && !defined(DCR_NO_PAD)
-        if (!EXACT && !DUPLEX) {        // diagnostic builds only: extra VALU issue per record
-            int dv;
-            asm volatile(".rept " DCR_STR(DCR_PADV) "\n v_mov_b32 %0, 0\n .endr" : "=v"(dv));
-        }
-#endif
-#if defined(DCR_PADM) && !defined(DCR_NO_PAD)
-        if (!EXACT && !DUPLEX) {        // diagnostic builds only: extra VMEM stores per record (range-checked out)
-            const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void *)a.rows, (short)0, 0, 0x00020000);
-#pragma unroll
-            for (int k = 0; k < DCR_PADM; ++k) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)lane, rz, lane, 64 * k, 0);
-        }
-#endif
-#if defined(DCR_PADL) && !defined(DCR_NO_PAD)
-        if (!EXACT && !DUPLEX) {        // diagnostic builds only: extra VMEM loads per record (range-checked out)
-            const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void *)a.rows, (short)0, 0, 0x00020000);
-            uint32_t acc = 0;
-#pragma unroll
-            for (int k = 0; k < DCR_PADL; ++k) acc += __builtin_amdgcn_raw_buffer_load_b32(rz, 4 * lane, 256 * k, 0);
-            asm volatile("" :: "v"(acc));
-        }
-#endif
-#if defined(DCR_PADS) && !defined(DCR_NO_PAD)
-        if (!EXACT && !DUPLEX) {        // diagnostic builds only: extra SALU issue per record
-            int ds;
-            asm volatile(".rept " DCR_STR(DCR_PADS) "\n s_mov_b32 %0, 0\n .endr" : "=s"(ds));
-        }
-#endif
         sp.mark(0);
         if (DCR_STAMP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         sp.mark(1);                    // [0] wait for this record's prefetched bytes
@@ -3998,29 +3892,18 @@ __global__ __launch_bounds__(fk::kBlockThreads, EXACT ? DCR_EXACT_OCC : DCR_FAST
         fast_load<DUPLEX>(a, m1, ML + (EXACT ? __builtin_amdgcn_readfirstlane(xv) : i3), lane, st);
         if (EXACT) xv = a.xlist[opaque(nxt(i3))];
         store_row(lane);
-        if (!EXACT && DCR_VMPAD > 0) {
-            // DCR_VMPAD stores that the range check drops (no memory access)
-            // right after the prefetch: every path through the record now
-            // issues at least that many VMEM ops after the prefetch's loads,
-            // so the next staging's wait for them (s_waitcnt vmcnt counts
-            // loads and stores in issue order) is vmcnt(DCR_VMPAD) or more,
-            // not a drain of this record's column stores
-            const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void *)a.rows, (short)0, 0, 0x00020000);
-#pragma unroll
-            for (int k = 0; k < DCR_VMPAD; ++k) __builtin_amdgcn_raw_buffer_store_b32(0u, rz, 4 * lane, 256 * k, 0);
-        }
         sp.mark(3);                    // [2] prefetch issue
         lds_fence();
         const uint2 rw = *(const uint2 *)(lds + rm_addr + 8 * lane);
         // the read's word relative to this record: col | len << 8 | mapq << 16, stage offset
-        const uint2 rm = make_uint2((uint32_t)(((int)rw.x >> 16) + ((DCR_ABL == 6 && !DUPLEX ? a.meta[0].d0 : m0.d0) & 0xFFFF)) |
+        const uint2 rm = make_uint2((uint32_t)(((int)rw.x >> 16) + (m0.d0 & 0xFFFF)) |
                                         (rw.x & 0xFFFFu) << 8,
-                                    rw.y - (DCR_ABL == 6 && !DUPLEX ? a.meta[0].base_al : m0.base_al));
+                                    rw.y - m0.base_al);
         const RecMeta m2 = meta_from_lanes(*(const uint32_t *)(lds + fk::kMv + 32 * wave + 4 * (lane & 7)));   // record i2
         // a record this kernel does not decide gets an empty row (kind 0:
         // k_fast_rows leaves its scalars to the kernel that finishes it)
         auto no_row = [&]() {
-            if (!EXACT && DCR_ROWS)     // the row's four words zeroed (kind 0), no lane branch
+            if (!EXACT)                 // the row's four words zeroed (kind 0), no lane branch
                 __builtin_amdgcn_raw_buffer_store_b32(0u, __builtin_amdgcn_make_buffer_rsrc((void *)(a.rows + i), (short)0, 16,
                                                                                             0x00020000), 4 * lane, 0, 0);
         };
@@ -4046,12 +3929,12 @@ __global__ __launch_bounds__(fk::kBlockThreads, EXACT ? DCR_EXACT_OCC : DCR_FAST
             // live columns in the earlier tiles, undecided, so such a (rare)
             // record takes the EXACT queue instead of being decided here
             int fin;
-            if (sg.T <= 64) fin = finish_record<DUPLEX, 1, EXACT>(a, m0, sg, lds, stage_addr, ov_addr, rm_addr, list_addr, lane, sp, s_xt, s_r1, s_qt, i, pd);
-            else if (sg.T <= 128) fin = finish_record<DUPLEX, 2, EXACT>(a, m0, sg, lds, stage_addr, ov_addr, rm_addr, list_addr, lane, sp, s_xt, s_r1, s_qt, i, pd);
-            else if (sg.T <= 192) fin = finish_record<DUPLEX, 3, EXACT>(a, m0, sg, lds, stage_addr, ov_addr, rm_addr, list_addr, lane, sp, s_xt, s_r1, s_qt, i, pd);
-            else fin = finish_record<DUPLEX, 4, EXACT>(a, m0, sg, lds, stage_addr, ov_addr, rm_addr, list_addr, lane, sp, s_xt, s_r1, s_qt, i, pd);
+            if (sg.T <= 64) fin = finish_record<DUPLEX, 1, EXACT>(a, m0, sg, lds, stage_addr, ov_addr, rm_addr, list_addr, lane, sp, s_xt, s_r1, s_qt, pd);
+            else if (sg.T <= 128) fin = finish_record<DUPLEX, 2, EXACT>(a, m0, sg, lds, stage_addr, ov_addr, rm_addr, list_addr, lane, sp, s_xt, s_r1, s_qt, pd);
+            else if (sg.T <= 192) fin = finish_record<DUPLEX, 3, EXACT>(a, m0, sg, lds, stage_addr, ov_addr, rm_addr, list_addr, lane, sp, s_xt, s_r1, s_qt, pd);
+            else fin = finish_record<DUPLEX, 4, EXACT>(a, m0, sg, lds, stage_addr, ov_addr, rm_addr, list_addr, lane, sp, s_xt, s_r1, s_qt, pd);
             if (!EXACT && fin != kFinDone) no_row();
-            if (!EXACT && DCR_DEFER && fin == kFinDone) row_i = i;
+            if (!EXACT && fin == kFinDone) row_i = i;
             if (!EXACT && fin == kFinQueue) {
                 if (lane == npend) pend = i;
                 if (++npend == kWave) flush(lane);
@@ -4110,7 +3993,6 @@ __global__ __launch_bounds__(256) void k_r2_table(const dcr_params *P, uint32_t 
 // double pairwise walk): the record goes on its queue.  Kind 2 rows carry an
 // E the fast kernel stored itself.
 __global__ __launch_bounds__(256) void k_fast_rows(FastArgs a) {
-    if (!DCR_ROWS) return;                       // rows are written (and zeroed) only by DCR_ROWS builds
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= *a.fast_count) return;
     const uint4 row = a.rows[i];
@@ -4155,9 +4037,6 @@ __global__ __launch_bounds__(256) void k_fast_rows(FastArgs a) {
 // again and the wave re-read its last index forever (the
 // round-1 hang).
 template <bool DUPLEX>
-#ifndef DCR_GEN_OCC
-#define DCR_GEN_OCC 2
-#endif
 __global__ __launch_bounds__(kBlock, DCR_GEN_OCC) void k_consensus_general(Args a) {
     __shared__ double2 s_lut[DCR_LUT_N];
     __shared__ double s_qthr[DCR_MAX_QTHRESH];
@@ -4237,7 +4116,7 @@ __global__ __launch_bounds__(256, DCR_LAYOCC) void k_ins_layout(Args a) {
         return nw + __builtin_amdgcn_readfirstlane(__shfl(t, leader, kWave));
     };
     uint64_t gacc[3] = {0, 0, 0}, gcnt[3] = {0, 0, 0}, gmax = 0;   // DCR_GSTAMP builds: ticks per record class
-    for (int i = blockIdx.x * kWavesPerBlock + wave; i < n; i = DCR_LAYCLAIM && !DUPLEX ? (nw >= n ? n : claim()) : i + nw) {
+    for (int i = blockIdx.x * kWavesPerBlock + wave; i < n; i = !DUPLEX ? (nw >= n ? n : claim()) : i + nw) {
         const uint64_t g0 = DCR_GSTAMP ? __builtin_amdgcn_s_memtime() : 0;
         const int vv = a.ws.ovf[i];
         if (vv < 0) continue;                         // decided by k_decide: no insertion column
@@ -4256,7 +4135,7 @@ __global__ __launch_bounds__(256, DCR_LAYOCC) void k_ins_layout(Args a) {
                 const int r = c + lane;
                 if (r < R) {
                     const ReadRef rd = get_read<DUPLEX>(a, rec, r);
-                    if (DCR_LAYHOIST && c == 0) {
+                    if (c == 0) {
                         rd0 = rd;
                         const int kl = max(rd.ncig - 1, 0);      // every load issued at once, clamped to the read's runs
                         const uint32_t v0 = rd.cig[0], v1 = rd.cig[min(1, kl)], v2 = rd.cig[min(2, kl)],
@@ -4288,7 +4167,7 @@ __global__ __launch_bounds__(256, DCR_LAYOCC) void k_ins_layout(Args a) {
                 bool isI = false, b_r = false;
                 uint32_t need = 0, L = 0, bb = 0, sr = 0;
                 if (r < R) {
-                    const bool reg = DCR_LAYHOIST && c == 0;
+                    const bool reg = c == 0;
                     const ReadRef rd = reg ? rd0 : get_read<DUPLEX>(a, rec, r);
                     const uint32_t *cg0 = &rt[16 * lane + 12];
                     int nIr = 0, acc = 0, accb = 0, mi = 0;
@@ -4382,7 +4261,7 @@ __global__ __launch_bounds__(256, DCR_LAYOCC) void k_ins_layout(Args a) {
                     // record of at most 64 reads, per chunk and block beyond
                     auto build_rt = [&](const int cb, const int nr) {
                     if (lane < nr) {
-                        const bool reg = DCR_LAYHOIST && cb == 0;
+                        const bool reg = cb == 0;
                         const ReadRef rd = reg ? rd0 : get_read<DUPLEX>(a, rec, cb + lane);
                         const uint4 cq = ((const uint4 *)&rt[16 * lane])[3];
                         const uint32_t cg0[4] = {cq.x, cq.y, cq.z, cq.w};
@@ -4412,7 +4291,7 @@ __global__ __launch_bounds__(256, DCR_LAYOCC) void k_ins_layout(Args a) {
                     }
                         lds_fence();
                     };
-                    const bool one = DCR_LAYHOIST && R <= kWave;
+                    const bool one = R <= kWave;
                     if (one) build_rt(0, R);
                     // pass 0 decides (no rows written); the rows only when some
                     // column stays undecided (pass 1)

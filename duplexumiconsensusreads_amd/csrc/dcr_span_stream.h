@@ -51,8 +51,6 @@ namespace dcr_span {
 
 constexpr int kSlots = 4;
 
-inline int32_t span_members(size_t k) { return k == 0 ? 128 : k == 1 ? 1024 : 4096; }
-
 // Every slot's buffers are sized once, for the largest span, by start() on
 // the opening thread before the producer exists: a span holds at most
 // kSpanMembers members, at most kSpanIn compressed bytes (a span ends early
@@ -60,12 +58,11 @@ inline int32_t span_members(size_t k) { return k == 0 ? 128 : k == 1 ? 1024 : 40
 // The producer's ensure() calls then never allocate or free (on the device:
 // no hipFree / hipHostMalloc on the producer thread while kernels run,
 // DESIGN.md §5, the round-3 exit suspect).
-#ifndef DCR_SPAN_MEMBERS
-#define DCR_SPAN_MEMBERS 4096   // A/B builds only
-#endif
-constexpr int32_t kSpanMembers = DCR_SPAN_MEMBERS;
+constexpr int32_t kSpanMembers = 4096;
 constexpr size_t kSpanIn = (size_t)128 << 20;
 constexpr size_t kSpanOut = (size_t)kSpanMembers * 65536;
+
+inline int32_t span_members(size_t k) { return k == 0 ? 128 : k == 1 ? 1024 : kSpanMembers; }
 
 template <class B>
 struct Stream {

@@ -25,9 +25,6 @@ struct FmtArgs {
     uint8_t *stream;                // formatted records
 };
 
-#ifndef DFL_CLAIM
-#define DFL_CLAIM 1   // pipeline k_deflate: blocks claimed from a counter (0: workgroup w takes w, w + grid, ...)
-#endif
 struct DflArgs {
     const uint8_t *stream;
     const int64_t *stream_bytes;    // device scalar (rec_off[2F])

@@ -450,9 +450,6 @@ __device__ __forceinline__ void p3c_header_wave(dfl::Shared &s, int lane) {
     }
 }
 
-#ifndef DFL_STAGE4
-#define DFL_STAGE4 1      // stage a block 16 bytes per lane per load, four loads in flight
-#endif
 // one workgroup (256 lanes) per BGZF block of the record stream
 __global__ __launch_bounds__(dfl::kT) void k_deflate(DflArgs D) {
     extern __shared__ __align__(16) uint8_t smem[];
@@ -467,20 +464,17 @@ __global__ __launch_bounds__(dfl::kT) void k_deflate(DflArgs D) {
     __shared__ uint64_t t[12];
     uint64_t t0 = 0;
     if (st && lane < 12) t[lane] = 0;
-#if DFL_CRCS
-    static_assert(DFL_CRCS == 4 || DFL_CRCS == 8, "CRC32 slices: 4 or 8");
-    // slice-by-N CRC32 tables, once per workgroup: t[0] the byte table,
+    // slice-by-8 CRC32 tables, once per workgroup: t[0] the byte table,
     // t[k][i] = t[k-1][i] >> 8 ^ t[0][t[k-1][i] & 255]
     for (int i = lane; i < 256; i += dfl::kT) s.crc_t[0][i] = dfl::crc_byte((uint32_t)i);
     __syncthreads();
-    for (int k = 1; k < DFL_CRCS; ++k) {
+    for (int k = 1; k < 8; ++k) {
         for (int i = lane; i < 256; i += dfl::kT) {
             const uint32_t v = s.crc_t[k - 1][i];
             s.crc_t[k][i] = (v >> 8) ^ s.crc_t[0][v & 255];
         }
         __syncthreads();
     }
-#endif
     auto stamp = [&](int k) {
         if (st && lane == 0) {
             const uint64_t now = __builtin_amdgcn_s_memtime();
@@ -507,7 +501,6 @@ __global__ __launch_bounds__(dfl::kT) void k_deflate(DflArgs D) {
         // stage the block as dwords (block starts are dword-aligned; the
         // record stream's allocation is padded), zero bytes past n
         {
-#if DFL_STAGE4
             // 16 bytes per lane per load, four loads in flight (block starts
             // are 16-byte aligned: 0xff00 = 16 * 4080)
             static_assert(dfl::kMaxIn % 16 == 0 && sizeof(s.in) % 16 == 0, "16-byte staging");
@@ -538,20 +531,6 @@ __global__ __launch_bounds__(dfl::kT) void k_deflate(DflArgs D) {
                     dst[i] = w;
                 }
             }
-#else
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(D.stream + off);
-            uint32_t *dst = reinterpret_cast<uint32_t *>(s.in);
-            const uint32_t nw = (n + 3) / 4, pw = (uint32_t)sizeof(s.in) / 4;
-            for (uint32_t i = lane; i < pw; i += dfl::kT) {
-                uint32_t v = 0;
-                if (i < nw) {
-                    v = src[i];
-                    const uint32_t rem = n - 4 * i;
-                    if (rem < 4) v &= (1u << (8 * rem)) - 1;
-                }
-                dst[i] = v;
-            }
-#endif
         }
         dfl::p0_clear(s, lane);
         __syncthreads();
@@ -568,31 +547,23 @@ __global__ __launch_bounds__(dfl::kT) void k_deflate(DflArgs D) {
         __syncthreads();
         stamp(3);
         dfl::p3c_trees(s, lane);
-#if DFL_CRC_LATE
         // waves 2 and 3 are idle while lanes 0 and 64 build the two codes:
         // the sub-block CRCs (two per lane) go there
-        static_assert(dfl::kT == 256, "DFL_CRC_LATE assumes four waves");
+        static_assert(dfl::kT == 256, "the sub-block CRCs on waves 2 and 3 assume four waves");
         if (lane >= 128) {
             s.lane_crc[lane - 128] = dfl::sub_crc(s, n, lane - 128);
             s.lane_crc[lane] = dfl::sub_crc(s, n, lane);
         }
-#endif
         __syncthreads();
         stamp(4);
         dfl::p3c_assign(s, lane);
         __syncthreads();
         stamp(10);
         if (lane < kW) p3c_header_wave(s, lane);
-#if DFL_CODES_EARLY
         else dfl::p3d_codes_litdist(s, lane - kW, dfl::kT - kW);   // waves 1-3, idle during the header
-#endif
         __syncthreads();
         stamp(11);
-#if DFL_CODES_EARLY
         if (lane < 19) s.cl_code[lane] = dfl::code_of(s.cl_len, lane, s.next_code[2]);
-#else
-        dfl::p3d_codes(s, lane);
-#endif
         __syncthreads();
         stamp(5);
         dfl::p4_bits(s, n, lane, tok);
@@ -601,9 +572,7 @@ __global__ __launch_bounds__(dfl::kT) void k_deflate(DflArgs D) {
         p4_scan_wg(s, n, lane, slot);
         __syncthreads();
         stamp(7);
-#ifndef DFL_ABL_NOEMIT
         dfl::p5_emit(s, n, lane, tok, slot);
-#endif
         __syncthreads();
         dfl::p6_copy(s, lane, slot);
         stamp(8);

@@ -1,7 +1,6 @@
 """GPU deflate phase probe: k_deflate over a formatted consensus stream with
 s_memtime phase stamps (dcr_deflate_probe, diagnostic entry of libdcr.so)."""
 import ctypes
-import os
 import sys
 import time
 import zlib
@@ -50,7 +49,7 @@ def main():
         # (the library's block size may differ from 0xff00: members are consecutive)
         rb = raw.tobytes()
         at = 0
-        for b in range(nb if not os.environ.get("DFL_NOVERIFY") else 0):
+        for b in range(nb):
             if not sizes[b]:
                 break
             mem = slots[b * 65536:b * 65536 + int(sizes[b])].tobytes()
@@ -58,9 +57,8 @@ def main():
             got = d.decompress(mem)
             assert d.eof and not d.unused_data and got == rb[at:at + len(got)], f"block {b} differs"
             at += len(got)
-        if not os.environ.get("DFL_NOVERIFY"):      # ablation builds (invalid members): timing only
-            assert at == len(rb), "members do not cover the stream"
-            nb = b + 1 if sizes[b] else b
+        assert at == len(rb), "members do not cover the stream"
+        nb = b + 1 if sizes[b] else b
         import hashlib
         hsh = hashlib.sha1()
         for b in range(nb):
