@@ -6,8 +6,9 @@
 //
 // Per batch the work splits into a serial walk (record boundaries, filters,
 // grouping, RNG; a few loads per record) and parallel parts (inflate of the
-// next window of BGZF blocks; per-read copies of sequence / qualities /
-// CIGAR into the caller's pinned arrays, queued by the walk as jobs).
+// next window of BGZF blocks; family checks and per-read copies of sequence /
+// qualities / CIGAR into the caller's pinned arrays, queued by the walk as
+// family tasks).
 //
 // Reference: /root/reference/DuplexUMIConsensusReads.py (":line" below).
 #include <zlib.h>
@@ -137,7 +138,7 @@ const SeqTable kSeq;
 
 // 4-bit BAM sequence -> ASCII letters: 16 packed bytes (32 bases) per step
 // with two byte shuffles of the 16-letter table (SSSE3, in x86-64-v2), the
-// tail by the pair table.  Part of the pack copy, which runs on the pool for
+// tail by the pair table.  Part of copy_read, which runs on the pool for
 // every read of a batch.
 inline void decode_seq(const uint8_t *s, int32_t l_seq, uint8_t *d) {
     const int32_t half = l_seq >> 1;
@@ -190,12 +191,25 @@ const FilterMsg kFilterMsg[] = {
     {DCR_ERR_EXIT, "ERROR: unexpected symbols (P, N, B, *) were found in CIGAR strings."},
     {DCR_ERR_EXIT, "ERROR: softclips (S) found in the middle of the read."}};
 
-struct Job {
-    size_t rec;         // window offset of the record
-    int64_t dst_base;
-    int64_t dst_cig;
-    int32_t read;       // batch read index: the per-read fields are written by the copy job
-};
+// One read into the batch: the record at offset rec of window w becomes read
+// i, its bases and qualities at dst_base, its CIGAR at dst_cig.
+inline void copy_read(const uint8_t *w, size_t rec, dcr_host_batch *b, int64_t i, int64_t dst_base, int64_t dst_cig) {
+    const uint8_t *r = w + rec + 4;
+    const uint32_t l_rn = r[8];
+    const uint32_t n_cig = rd16(r + 12);
+    const int32_t l_seq = rdi32(r + 16);
+    b->read_pos[i] = rdi32(r + 4);
+    b->read_mapq[i] = r[9];
+    b->seq_len[i] = l_seq;
+    b->seq_off[i] = dst_base;
+    b->cig_off[i] = (int32_t)dst_cig;
+    b->cig_n[i] = (int32_t)n_cig;
+    const uint8_t *cig = r + 32 + l_rn;
+    std::memcpy(b->cigar + dst_cig, cig, 4u * n_cig);
+    const uint8_t *sq = cig + 4u * n_cig;
+    decode_seq(sq, l_seq, b->bases + dst_base);
+    std::memcpy(b->quals + dst_base, sq + ((l_seq + 1) >> 1), (size_t)l_seq);
+}
 
 }  // namespace
 
@@ -1046,7 +1060,7 @@ class Inflater {
 // DCR_INGEST_PROF=1: seconds per ingest stage, printed to stderr at close
 struct IngestProf {
     bool on = std::getenv("DCR_INGEST_PROF") != nullptr;
-    double wait_chunk = 0, scan = 0, parse = 0, flush = 0, walk_total = 0, complete = 0, tasks_wait = 0;
+    double wait_chunk = 0, scan = 0, parse = 0, walk_total = 0, complete = 0, tasks_wait = 0;
     int64_t indexed = 0;
     static double now() {
         return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -1057,7 +1071,7 @@ struct dcr_ingest {
     FILE *f = nullptr;
     IngestProf prof;
     dcr_ingest_cfg cfg{};
-    std::unique_ptr<Pool> pool;          // pack jobs (on the packer thread, below)
+    std::unique_ptr<Pool> pool;          // family tasks (on the packer thread, below)
     std::unique_ptr<Pool> ppool;         // record parse of serially scanned records (walk thread)
     std::unique_ptr<Inflater> infl;
     RecParser rp;
@@ -1088,19 +1102,16 @@ struct dcr_ingest {
     // counters :1508
     int64_t passed = 0, excluded = 0, processed = 0, filtered = 0, records = 0;
     PyRandom rng;
-    // pack jobs of the current batch
-    std::vector<Job> jobs;
     std::vector<int> idx_tmp;
 
     ~dcr_ingest() {
         pk_stop_thread();
         if (prof.on)
             std::fprintf(stderr,
-                         "[ingest] walk %.3f s: chunk wait %.3f, serial scan %.3f, parse %.3f, pack copy %.3f, "
+                         "[ingest] walk %.3f s: chunk wait %.3f, serial scan %.3f, parse %.3f, "
                          "families %.3f, family tasks wait %.3f; scanner stage: chain %.3f, parse %.3f; indexed "
                          "records %lld of %lld\n",
-                         prof.walk_total, prof.wait_chunk, prof.scan, prof.parse, prof.flush, prof.complete,
-                         prof.tasks_wait,
+                         prof.walk_total, prof.wait_chunk, prof.scan, prof.parse, prof.complete, prof.tasks_wait,
                          infl ? infl->scan_s : 0.0,
                          infl ? infl->index_parse_s : 0.0, (long long)prof.indexed, (long long)records);
         infl.reset();             // stops the inflate thread before the file closes
@@ -1126,7 +1137,6 @@ struct dcr_ingest {
                     release_retired();
                 }
             }
-            flush_jobs();                           // the pack jobs point into it too
             const double tw = prof.on ? IngestProf::now() : 0;
             Chunk *nx = infl->next();
             if (prof.on) prof.wait_chunk += IngestProf::now() - tw;
@@ -1168,46 +1178,54 @@ struct dcr_ingest {
         return 1;
     }
 
-    // -- pack jobs -------------------------------------------------------------
-    // The walk appends a job per read it packs; every kPkStep jobs it hands
-    // the new ones to the packer thread, which copies them on the pool while
-    // the walk goes on (the copy had run between walk steps, the walk waiting
-    // for it: ~40 % of an ingest).  Jobs point into the current window and
-    // the batch, so the walk waits for the packer before the window moves
-    // (need()) and before the batch is handed out (next()).  `jobs` is
-    // reserved for the batch's reads, so it never reallocates under the packer.
+    // -- family tasks ----------------------------------------------------------
+    // The walk reserves every family in the batch -- its table entry, names,
+    // read / base / CIGAR / side-byte ranges and column offsets, all sizes
+    // known from one pass over its records (reserve_family) -- and queues
+    // the rest as a task: the UMI and rname checks, the split and the
+    // per-read fields and copies.  Every kTkReads queued reads it hands the
+    // new tasks to the packer thread, which runs them on the pool, in items
+    // of about kItemReads reads, while the walk goes on.  A family that
+    // samples is checked and sampled by the walk itself, after every queued
+    // task that still has its check to run (the checks of earlier families
+    // come first, :1548-1551; a task of an earlier sampled family cannot
+    // fail and is not waited for); its task then only copies the picked
+    // reads.  Tasks point
+    // into the window, the records and the batch, so they are drained
+    // (flush_tasks) before a window of the leftover buffers or the serial
+    // scan's records change and before the batch is handed out (next()); a
+    // chunk window is retired and given back once they have run.  The first
+    // task (in input order) that fails truncates the batch to its
+    // reservation and stops there, where the reference stops.  `tasks` and
+    // `pend_recs` are reserved for the batch, and drained before they would
+    // grow, so they never reallocate under the packer.
     dcr_host_batch *hb = nullptr;
-    static constexpr size_t kPkStep = 4096;
     std::thread pk_th;
     std::mutex pk_mu;
     std::condition_variable pk_cv;
-    size_t pk_sub = 0, pk_done = 0;      // jobs [0, pk_sub) handed over, [0, pk_done) copied
+    size_t tk_sub = 0, tk_done = 0;      // tasks [0, tk_sub) handed over, [0, tk_done) run
+    static constexpr size_t kTkReads = 8192, kItemReads = 1024;   // 256 and 32 families of 4 x 8 reads
+    size_t tk_reads = 0;                 // reads queued since the last hand-over
+    size_t tk_unchecked = 0;             // queued tasks with their check still to run
     bool pk_quit = false;
-    const uint8_t *pk_w = nullptr;       // the window and batch of the handed-over jobs
-    dcr_host_batch *pk_b = nullptr;
+    dcr_host_batch *pk_b = nullptr;      // the batch of the handed-over tasks
 
     void pk_start_thread() {
         pk_th = std::thread([this] {
             for (;;) {
-                size_t j0, j1, t0, t1;
-                const uint8_t *w;
+                size_t t0, t1;
                 dcr_host_batch *b;
                 {
                     std::unique_lock<std::mutex> lk(pk_mu);
-                    pk_cv.wait(lk, [&] { return pk_quit || pk_sub > pk_done || tk_sub > tk_done; });
+                    pk_cv.wait(lk, [&] { return pk_quit || tk_sub > tk_done; });
                     if (pk_quit) return;
-                    j0 = pk_done;
-                    j1 = pk_sub;
                     t0 = tk_done;
                     t1 = tk_sub;
-                    w = pk_w;
                     b = pk_b;
                 }
-                if (t1 > t0) run_tasks(b, t0, t1);
-                if (j1 > j0) pack_range(w, b, jobs.data(), j0, j1);
+                run_tasks(b, t0, t1);
                 {
                     std::lock_guard<std::mutex> g(pk_mu);
-                    pk_done = j1;
                     tk_done = t1;
                 }
                 pk_cv.notify_all();
@@ -1223,29 +1241,6 @@ struct dcr_ingest {
         pk_cv.notify_all();
         pk_th.join();
     }
-    // hand the jobs appended since the last hand-over to the packer
-    void kick_jobs(bool force) {
-        if (jobs.size() == pk_sub || (!force && jobs.size() - pk_sub < kPkStep)) return;
-        {
-            std::lock_guard<std::mutex> g(pk_mu);
-            pk_sub = jobs.size();
-            pk_w = wb;
-            pk_b = hb;
-        }
-        pk_cv.notify_all();
-    }
-    // -- deferred family completion --------------------------------------------
-    // A family with nothing to sample (the common case) is reserved by the
-    // walk -- its table entry, names, read / base / CIGAR / side-byte ranges
-    // and column offsets, all sizes known from one pass over its records --
-    // and the rest of complete_family (the UMI and rname checks, the split
-    // and the per-read fields and copies) runs as a task on the packer thread
-    // and its pool while the walk goes on.  Tasks point into the window and
-    // the records, so they are drained (flush_tasks) before either changes,
-    // before a family that samples (the checks of earlier families come
-    // first, :1548-1551) and at the end of a batch; the first task (in input
-    // order) that fails truncates the batch to its reservation and stops
-    // there, exactly where complete_family would have stopped.
     // a family's records: a pointer list, or (p null) consecutive records
     struct RecList {
         const Rec *const *p;
@@ -1256,6 +1251,7 @@ struct dcr_ingest {
         const uint8_t *w;               // the window its records' offsets refer to
         uint32_t rb, n;                 // the family's records: pend_recs[rb, rb + n), or cbase[0, n)
         const Rec *cbase = nullptr;     // set when they are consecutive in the record index (no copy)
+        bool checked = false;           // the walk ran check_family already (a family that sampled)
         int32_t t, f;                   // table entry; processed family (-1: filtered)
         int64_t read_base, base_off[4], cig_off[4];   // per subfamily (split order)
         int64_t filt_off;               // filtered: its bytes in side_filt
@@ -1285,14 +1281,14 @@ struct dcr_ingest {
             retired.pop_front();
         }
     }
-    size_t tk_sub = 0, tk_done = 0;      // tasks [0, tk_sub) handed over, [0, tk_done) run
-    static constexpr size_t kTkStep = 256;
 
     void run_task(FamTask &T, const uint8_t *w, dcr_host_batch *b) const {
         const RecList fr{T.cbase ? nullptr : pend_recs.data() + T.rb, T.cbase};
-        std::string umi2;
-        T.err_kind = check_family(fr, T.n, w, umi2, T.err);
-        if (T.err_kind != DCR_ERR_NONE) return;
+        if (!T.checked) {
+            std::string umi2;
+            T.err_kind = check_family(fr, T.n, w, umi2, T.err);
+            if (T.err_kind != DCR_ERR_NONE) return;
+        }
         if (T.f < 0) {                  // filtered: its reads to _filteredfamilies.bam in input order
             int64_t o = T.filt_off;
             for (uint32_t i = 0; i < T.n; ++i) {
@@ -1301,7 +1297,7 @@ struct dcr_ingest {
             }
             return;
         }
-        // split_family order: subfamily k's reads in input order after those of k - 1
+        // split_family order: subfamily k's reads in list order after those of k - 1
         int64_t ri[4], bo[4], co[4];
         int64_t acc = T.read_base;
         for (int k = 0; k < 4; ++k) {
@@ -1314,40 +1310,34 @@ struct dcr_ingest {
             const Rec &rc = *fr[j];
             const int k = rc.subk;
             if (k < 0) continue;
-            const uint8_t *r = w + rc.off + 4;
-            const uint32_t l_rn = r[8];
-            const uint32_t n_cig = rd16(r + 12);
-            const int32_t l_seq = rdi32(r + 16);
-            const int64_t i = ri[k]++;
-            b->read_pos[i] = rdi32(r + 4);
-            b->read_mapq[i] = r[9];
-            b->seq_len[i] = l_seq;
-            b->seq_off[i] = bo[k];
-            b->cig_off[i] = (int32_t)co[k];
-            b->cig_n[i] = (int32_t)n_cig;
-            const uint8_t *cig = r + 32 + l_rn;
-            std::memcpy(b->cigar + co[k], cig, 4u * n_cig);
-            const uint8_t *sq = cig + 4u * n_cig;
-            decode_seq(sq, l_seq, b->bases + bo[k]);
-            std::memcpy(b->quals + bo[k], sq + ((l_seq + 1) >> 1), (size_t)l_seq);
-            bo[k] += l_seq;
-            co[k] += n_cig;
+            copy_read(w, rc.off, b, ri[k]++, bo[k], co[k]);
+            bo[k] += rc.l_seq;
+            co[k] += rc.n_cig;
         }
     }
+    std::vector<size_t> item_cut;        // packer thread: pool item c runs tasks [item_cut[c], item_cut[c + 1])
     void run_tasks(dcr_host_batch *b, size_t t0, size_t t1) {
-        const size_t chunk = 32;
-        pool->run((t1 - t0 + chunk - 1) / chunk, [&](size_t c) {
-            const size_t te = std::min(t1, t0 + (c + 1) * chunk);
-            for (size_t t = t0 + c * chunk; t < te; ++t) run_task(tasks[t], tasks[t].w, b);
+        item_cut.assign(1, t0);
+        size_t reads = 0;
+        for (size_t t = t0; t < t1; ++t) {
+            reads += tasks[t].n;
+            if (reads >= kItemReads || t + 1 == t1) {
+                item_cut.push_back(t + 1);
+                reads = 0;
+            }
+        }
+        pool->run(item_cut.size() - 1, [&](size_t c) {
+            for (size_t t = item_cut[c]; t < item_cut[c + 1]; ++t) run_task(tasks[t], tasks[t].w, b);
             return true;
         });
     }
+    // hand the tasks queued since the last hand-over to the packer
     void kick_tasks(bool force) {
-        if (tasks.size() == tk_sub || (!force && tasks.size() - tk_sub < kTkStep)) return;
+        if (tasks.size() == tk_sub || (!force && tk_reads < kTkReads)) return;
+        tk_reads = 0;
         {
             std::lock_guard<std::mutex> g(pk_mu);
             tk_sub = tasks.size();
-            pk_w = wb;
             pk_b = hb;
         }
         pk_cv.notify_all();
@@ -1391,71 +1381,78 @@ struct dcr_ingest {
         tasks.clear();
         pend_recs.clear();
         task_recs.clear();
+        tk_unchecked = 0;
         return rc;
     }
 
-    // preprocess_family for a family that samples nothing, deferred (above);
-    // a family that samples, or that the reservation cannot describe, takes
-    // complete_family after the queued tasks.  Returns as complete_family.
-    int queue_family() {
-        dcr_host_batch *b = hb;
-        const Rec &r0 = *fam.front();
-        int64_t nb = 0, nc = 0, filt_bytes = 0;
+    // What the batch layout needs to know of a list of reads: the whole
+    // list's totals, and per subfamily (split_family :132-154, from parse_at)
+    // the reads, bases, CIGAR ops, column bounds, '=' / 'X' reads and first read.
+    struct FamSum {
+        int64_t n = 0, nb = 0, nc = 0, bytes = 0;
         int64_t cnt[4] = {0, 0, 0, 0}, nbk[4] = {0, 0, 0, 0}, nck[4] = {0, 0, 0, 0};
-        int64_t mn[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0};
+        int64_t mn[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0};   // min pos, max end_kept
         int16_t eqx[4] = {0, 0, 0, 0};
         const Rec *first[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (const Rec *r : fam) {
-            nb += r->l_seq;
-            nc += r->n_cig;
-            filt_bytes += r->len;
+    };
+    static FamSum summarize(const Rec *const *rs, size_t n) {
+        FamSum S;
+        S.n = (int64_t)n;
+        for (size_t i = 0; i < n; ++i) {
+            const Rec *r = rs[i];
+            S.nb += r->l_seq;
+            S.nc += r->n_cig;
+            S.bytes += r->len;
             const int k = r->subk;
             if (k < 0) continue;
-            if (!first[k]) {
-                first[k] = r;
-                mn[k] = r->pos;
-                mx[k] = r->end_kept;
+            if (!S.first[k]) {
+                S.first[k] = r;
+                S.mn[k] = r->pos;
+                S.mx[k] = r->end_kept;
             } else {
-                if (r->pos < mn[k]) mn[k] = r->pos;
-                if (r->end_kept > mx[k]) mx[k] = r->end_kept;
+                if (r->pos < S.mn[k]) S.mn[k] = r->pos;
+                if (r->end_kept > S.mx[k]) S.mx[k] = r->end_kept;
             }
-            ++cnt[k];
-            nbk[k] += r->l_seq;
-            nck[k] += r->n_cig;
-            if (eqx[k] < 0x7fff && r->eqx) ++eqx[k];
+            ++S.cnt[k];
+            S.nbk[k] += r->l_seq;
+            S.nck[k] += r->n_cig;
+            if (S.eqx[k] < 0x7fff && r->eqx) ++S.eqx[k];
         }
-        bool samples = false, enough = true;
-        for (int k = 0; k < 4; ++k) {                      // check_number_reads (:157-188)
-            if (cnt[k] < cfg.min_reads) { enough = false; break; }
-            if (cnt[k] > cfg.max_reads) { samples = true; break; }
-        }
-        const size_t l_code = r0.l_code;
-        // the RX written below is that of the first A1 and B1 read, whose
-        // length the deferred UMI check (run_task) has not yet tied to r0's
-        const int64_t l_rx0 = first[0] ? first[0]->l_rx : 0, l_rx2 = first[2] ? first[2]->l_rx : 0;
-        const int64_t names_need = (int64_t)l_code + 1 + (l_rx0 + 1) + (l_rx2 + 1) + 64 * 2;
-        // the family's records consecutive in the record index (not copies in fam_store)?
-        bool contig = fam.front() < fam_store.data() || fam.front() >= fam_store.data() + fam_store.size();
-        for (size_t j = 1; j < fam.size() && contig; ++j) contig = fam[j] == fam.front() + j;
-        if (samples || (!contig && pend_recs.size() + fam.size() > pend_recs.capacity()) ||
-            tasks.size() == tasks.capacity()) {
-            if (flush_tasks() < 0) return -1;
-            return complete_family();
-        }
-        const bool fits = b->n_tab < b->cap_tab && b->n_fam < b->cap_fam &&
-                          b->n_reads + (int64_t)fam.size() <= b->cap_reads && b->n_bases + nb <= b->cap_bases &&
-                          b->n_cigar + nc <= b->cap_cigar && b->n_names + names_need <= b->cap_names &&
-                          b->n_side_filt + filt_bytes <= b->cap_side;
-        if (!fits) {
-            if (b->n_tab == 0 && b->n_side_exc == 0) {
-                if (flush_tasks() < 0) return -1;
-                return fail_capacity("one family exceeds the batch capacities");
-            }
-            return 0;
-        }
+        return S;
+    }
+
+    // Is there room in the batch for the open family, all its reads counted
+    // (the bound also of a family that samples, tested before any draw)?
+    // Names: reserve_family writes the code and two RX strings, those of the
+    // first A1 and B1 read of the list it is given.  For a family checked
+    // later, on the packer, that list is the input and the two are S.first[0]
+    // and S.first[2], of any length: the check has not yet tied them to the
+    // first record's.  For a family that samples the list is the sample, not
+    // yet drawn here, but reserved only after check_family: every RX is then
+    // the first record's or its swapped halves, no longer than it.  Twice the
+    // longest of the three covers both.
+    bool family_fits(const FamSum &S) const {
+        const dcr_host_batch *b = hb;
+        const Rec &r0 = *fam.front();
+        int64_t l_rx = r0.l_rx;
+        for (int k = 0; k < 4; k += 2)
+            if (S.first[k]) l_rx = std::max<int64_t>(l_rx, S.first[k]->l_rx);
+        const int64_t names_need = (int64_t)r0.l_code + 1 + 2 * (l_rx + 1) + 64 * 2;
+        return b->n_tab < b->cap_tab && b->n_fam < b->cap_fam && b->n_reads + S.n <= b->cap_reads &&
+               b->n_bases + S.nb <= b->cap_bases && b->n_cigar + S.nc <= b->cap_cigar &&
+               b->n_names + names_need <= b->cap_names && b->n_side_filt + S.bytes <= b->cap_side;
+    }
+
+    // The open family's place in the batch, from the summary of the reads it
+    // packs (all of them, or the sample): table entry, names and counters;
+    // filtered (!enough), filt_bytes of side_filt; else the processed family's
+    // entries and its read / base / CIGAR / column ranges.  Returns the task
+    // with the offsets and the state before the family; its records, window
+    // and `checked` are the caller's to set.
+    FamTask reserve_family(const FamSum &S, int sampled, bool enough, int64_t filt_bytes) {
+        dcr_host_batch *b = hb;
+        const Rec &r0 = *fam.front();
         FamTask T;
-        T.rb = (uint32_t)pend_recs.size();
-        T.n = (uint32_t)fam.size();
         T.fam_before = b->n_fam;
         T.names_before = b->n_names;
         T.exc_before = b->n_side_exc;
@@ -1470,17 +1467,17 @@ struct dcr_ingest {
         T.c_filtered = filtered;
         const int32_t t = b->n_tab++;
         T.t = t;
-        b->tab_sampled[t] = 0;
+        b->tab_sampled[t] = sampled;
         b->tab_exc_cut[t] = b->n_side_exc;
         b->tab_filt_cut[t] = b->n_side_filt;
-        b->tab_code[t] = put_name(code_of(r0), l_code);
+        b->tab_code[t] = put_name(code_of(r0), r0.l_code);
         const int64_t code_off = b->tab_code[t];
         int64_t bo = b->n_bases, co = b->n_cigar;
         for (int k = 0; k < 4; ++k) {
             T.base_off[k] = bo;
             T.cig_off[k] = co;
-            bo += nbk[k];
-            co += nck[k];
+            bo += S.nbk[k];
+            co += S.nck[k];
         }
         if (!enough) {
             b->tab_kind[t] = DCR_FAM_FILTERED;
@@ -1489,40 +1486,129 @@ struct dcr_ingest {
             T.filt_off = b->n_side_filt;
             b->n_side_filt += filt_bytes;
             ++filtered;
-        } else {
-            const int32_t f = b->n_fam++;
-            T.f = f;
-            T.filt_off = 0;
-            b->tab_kind[t] = DCR_FAM_PROCESSED;
-            b->tab_proc[t] = f;
-            b->fam_tid[f] = r0.tid;
-            b->fam_code[f] = code_off;
-            for (int k = 0; k < 4; ++k) {
-                b->fam_eqx[4 * f + k] = (uint16_t)eqx[k];
-                b->sub_off[4 * f + k + 1] = b->sub_off[4 * f + k] + cnt[k];
-                const int64_t tt = (std::max<int64_t>(mx[k] - mn[k], 1) + 15) & ~(int64_t)15;
-                b->ss_col_off[4 * f + k + 1] = b->ss_col_off[4 * f + k] + tt;
-            }
-            for (int j = 0; j < 2; ++j) {
-                const int a = 2 * j, c = 2 * j + 1;
-                int64_t tt = std::max(mx[a], mx[c]) - std::min(mn[a], mn[c]);
-                tt = (std::max<int64_t>(tt, 1) + 15) & ~(int64_t)15;
-                b->ds_col_off[2 * f + j + 1] = b->ds_col_off[2 * f + j] + tt;
-            }
-            b->n_reads = b->sub_off[4 * f + 4];
-            b->n_bases = bo;
-            b->n_cigar = co;
-            b->ss_cols = b->ss_col_off[4 * f + 4];
-            b->ds_cols = b->ds_col_off[2 * f + 2];
-            // writer metadata: RX of the read0 of A1 and of B1 (:1367 via add_tags)
-            for (int j = 0; j < 2; ++j) {
-                const Rec *r = first[2 * j];
-                if (!r) b->fam_rx[2 * f + j] = put_name("", 0);
-                else b->fam_rx[2 * f + j] = put_name(rx_of(*r), r->l_rx);
-            }
-            ++processed;
+            return T;
         }
+        const int32_t f = b->n_fam++;
+        T.f = f;
+        T.filt_off = 0;
+        b->tab_kind[t] = DCR_FAM_PROCESSED;
+        b->tab_proc[t] = f;
+        b->fam_tid[f] = r0.tid;
+        b->fam_code[f] = code_off;
+        for (int k = 0; k < 4; ++k) {
+            b->fam_eqx[4 * f + k] = (uint16_t)S.eqx[k];
+            b->sub_off[4 * f + k + 1] = b->sub_off[4 * f + k] + S.cnt[k];
+            const int64_t tt = (std::max<int64_t>(S.mx[k] - S.mn[k], 1) + 15) & ~(int64_t)15;
+            b->ss_col_off[4 * f + k + 1] = b->ss_col_off[4 * f + k] + tt;
+        }
+        for (int j = 0; j < 2; ++j) {
+            const int a = 2 * j, c = 2 * j + 1;
+            int64_t tt = std::max(S.mx[a], S.mx[c]) - std::min(S.mn[a], S.mn[c]);
+            tt = (std::max<int64_t>(tt, 1) + 15) & ~(int64_t)15;
+            b->ds_col_off[2 * f + j + 1] = b->ds_col_off[2 * f + j] + tt;
+        }
+        b->n_reads = b->sub_off[4 * f + 4];
+        b->n_bases = bo;
+        b->n_cigar = co;
+        b->ss_cols = b->ss_col_off[4 * f + 4];
+        b->ds_cols = b->ds_col_off[2 * f + 2];
+        // writer metadata: RX of the read0 of A1 and of B1 (:1367 via add_tags)
+        for (int j = 0; j < 2; ++j) {
+            const Rec *r = S.first[2 * j];
+            if (!r) b->fam_rx[2 * f + j] = put_name("", 0);
+            else b->fam_rx[2 * f + j] = put_name(rx_of(*r), r->l_rx);
+        }
+        ++processed;
+        return T;
+    }
+
+    // check_number_reads' draws (:157-188) for the open family, whose
+    // subfamilies `sampled` names exceed max_reads: random.sample per
+    // subfamily in order, then `pick` holds the family's reads to pack, in
+    // split order, a sampled subfamily's in selection order.  1 done, -1 the
+    // state gate gave no state.
+    std::vector<const Rec *> split, pick;
+    int sample_family(const FamSum &S, int sampled) {
+        if (gate_fn && !gate_open) {
+            gate_open = true;
+            if (gate_fn(gate_user, rng.mt, &rng.index) != 0 || rng.index < 0 || rng.index > 624) {
+                g_err = "the state gate gave no generator state";
+                return -1;
+            }
+        }
+        // split_family (:132-154): subfamily k's reads at split[at[k], at[k] + cnt[k]), input order
+        size_t at[4], fill[4], n_split = 0;
+        for (int k = 0; k < 4; ++k) {
+            at[k] = fill[k] = n_split;
+            n_split += (size_t)S.cnt[k];
+        }
+        split.resize(n_split);
+        for (const Rec *r : fam)
+            if (r->subk >= 0) split[fill[r->subk]++] = r;
+        pick.clear();
+        for (int k = 0; k < 4; ++k) {
+            const Rec *const *sk = split.data() + at[k];
+            if (!(sampled >> k & 1)) {
+                pick.insert(pick.end(), sk, sk + S.cnt[k]);
+                continue;
+            }
+            rng.sample((int)S.cnt[k], cfg.max_reads, idx_tmp);
+            sample_calls.push_back((int32_t)S.cnt[k]);
+            sample_calls.push_back(cfg.max_reads);
+            for (int j : idx_tmp) pick.push_back(sk[j]);
+        }
+        return 1;
+    }
+
+    // preprocess_family up to the read loop (:1248-1264) for the open family:
+    // reserve it in the batch and queue its checks and copies.  A family that
+    // samples comes after every queued check and is checked and sampled
+    // here, in input order.  Returns 1 done, 0 no room in this batch (nothing
+    // changed, no draw made), -1 the reference stops here (batch error set)
+    // or the ingest fails.
+    int queue_family() {
+        dcr_host_batch *b = hb;
+        FamSum S = summarize(fam.data(), fam.size());
+        const int64_t filt_bytes = S.bytes;
+        int sampled = 0;
+        bool enough = true;
+        for (int k = 0; k < 4; ++k) {                      // check_number_reads (:157-188)
+            if (S.cnt[k] < cfg.min_reads) { enough = false; break; }
+            if (S.cnt[k] > cfg.max_reads) sampled |= 1 << k;
+        }
+        // the family's records consecutive in the record index (not copies in fam_store)?
+        bool contig = !sampled && (fam.front() < fam_store.data() || fam.front() >= fam_store.data() + fam_store.size());
+        for (size_t j = 1; j < fam.size() && contig; ++j) contig = fam[j] == fam.front() + j;
+        if (((sampled && tk_unchecked) || (!contig && pend_recs.size() + fam.size() > pend_recs.capacity()) ||
+             tasks.size() == tasks.capacity()) &&
+            flush_tasks() < 0)
+            return -1;
+        if (!family_fits(S)) {
+            if (b->n_tab == 0 && b->n_side_exc == 0) {
+                if (flush_tasks() < 0) return -1;
+                return fail_capacity("one family exceeds the batch capacities");
+            }
+            return 0;
+        }
+        const Rec *const *recs = fam.data();
+        size_t n = fam.size();
+        if (sampled) {
+            std::string msg;
+            const int kind = check_family(RecList{fam.data(), nullptr}, fam.size(), wb, umi2_, msg);
+            if (kind != DCR_ERR_NONE) return stop(kind, msg);
+            if (cfg.max_reads < 0) return stop(DCR_ERR_VALUE, "Sample larger than population or is negative");
+            if (sample_family(S, sampled) < 0) return -1;
+            if (enough) {
+                S = summarize(pick.data(), pick.size());
+                recs = pick.data();
+                n = pick.size();
+            }
+        }
+        FamTask T = reserve_family(S, sampled, enough, filt_bytes);
         T.w = wb;
+        T.checked = sampled != 0;
+        T.rb = (uint32_t)pend_recs.size();
+        T.n = (uint32_t)n;
         // consecutive records of the record index (the common case): the task
         // points at them, no per-record copy into pend_recs (whose 8-byte
         // writes each cost a write-allocate miss: 25 cycles per read).
@@ -1532,7 +1618,8 @@ struct dcr_ingest {
         if (contig) {
             T.cbase = fam.front();
         } else {
-            for (const Rec *r : fam) {
+            for (size_t j = 0; j < n; ++j) {
+                const Rec *r = recs[j];
                 if (r >= fs0 && r < fs1) {
                     task_recs.push_back(*r);
                     pend_recs.push_back(&task_recs.back());
@@ -1541,53 +1628,11 @@ struct dcr_ingest {
                 }
             }
         }
+        tk_reads += n;
+        tk_unchecked += !sampled;
         tasks.push_back(std::move(T));
-        if (tasks.size() - tk_sub >= kTkStep) release_retired();
+        if (tk_reads >= kTkReads) release_retired();
         return 1;
-    }
-
-    void flush_jobs() {
-        if (jobs.empty()) return;
-        const double tf = prof.on ? IngestProf::now() : 0;
-        struct Acc {
-            double &d, t;
-            bool on;
-            ~Acc() { if (on) d += IngestProf::now() - t; }
-        } acc{prof.flush, tf, prof.on};
-        kick_jobs(true);
-        {
-            std::unique_lock<std::mutex> lk(pk_mu);
-            pk_cv.wait(lk, [&] { return pk_done == pk_sub; });
-            pk_sub = pk_done = 0;
-        }
-        jobs.clear();
-    }
-    void pack_range(const uint8_t *w, dcr_host_batch *b, const Job *jobv, size_t j0, size_t j1) {
-        const size_t chunk = 2048;
-        const size_t nchunks = (j1 - j0 + chunk - 1) / chunk;
-        pool->run(nchunks, [&](size_t c) {
-            const size_t je = std::min(j1, j0 + (c + 1) * chunk);
-            for (size_t j = j0 + c * chunk; j < je; ++j) {
-                const Job &jb = jobv[j];
-                const uint8_t *r = w + jb.rec + 4;
-                const uint32_t l_rn = r[8];
-                const uint32_t n_cig = rd16(r + 12);
-                const int32_t l_seq = rdi32(r + 16);
-                const int32_t i = jb.read;
-                b->read_pos[i] = rdi32(r + 4);
-                b->read_mapq[i] = r[9];
-                b->seq_len[i] = l_seq;
-                b->seq_off[i] = jb.dst_base;
-                b->cig_off[i] = (int32_t)jb.dst_cig;
-                b->cig_n[i] = (int32_t)n_cig;
-                const uint8_t *cig = r + 32 + l_rn;
-                std::memcpy(b->cigar + jb.dst_cig, cig, 4u * n_cig);
-                const uint8_t *s = cig + 4u * n_cig;
-                decode_seq(s, l_seq, b->bases + jb.dst_base);
-                std::memcpy(b->quals + jb.dst_base, s + ((l_seq + 1) >> 1), (size_t)l_seq);
-            }
-            return true;
-        });
     }
 
     // parsed records ahead of the walk: rqp[rq_pos, rq_n) (the scanner's
@@ -1740,128 +1785,6 @@ struct dcr_ingest {
         return DCR_ERR_NONE;
     }
 
-    std::vector<const Rec *> sub[4];
-
-    // preprocess_family up to the read loop (:1248-1264), then pack or file
-    // the family.  Returns 1 done, 0 no room in this batch (nothing changed),
-    // -1 the reference stops at this family (batch error set).
-    int complete_family() {
-        dcr_host_batch *b = hb;
-        const Rec &r0 = *fam.front();
-        const char *code = code_of(r0);
-        const size_t l_code = r0.l_code;
-        // capacity check first, with the unsampled family as the bound
-        int64_t nb = 0, nc = 0, filt_bytes = 0;
-        for (const Rec *r : fam) { nb += r->l_seq; nc += r->n_cig; filt_bytes += r->len; }
-        const int64_t nfam_reads = (int64_t)fam.size();
-        const int64_t names_need = (int64_t)l_code + 1 + 2 * (int64_t)(r0.l_rx + 1) + 64 * 2;
-        const bool fits = b->n_tab < b->cap_tab && b->n_fam < b->cap_fam &&
-                          b->n_reads + nfam_reads <= b->cap_reads && b->n_bases + nb <= b->cap_bases &&
-                          b->n_cigar + nc <= b->cap_cigar && b->n_names + names_need <= b->cap_names &&
-                          b->n_side_filt + filt_bytes <= b->cap_side;
-        if (!fits) {
-            if (b->n_tab == 0 && b->n_side_exc == 0)
-                return fail_capacity("one family exceeds the batch capacities");
-            return 0;
-        }
-        {
-            std::string msg;
-            const int kind = check_family(RecList{fam.data(), nullptr}, fam.size(), wb, umi2_, msg);
-            if (kind != DCR_ERR_NONE) return stop(kind, msg);
-        }
-        // split_family (:132-154), the subfamily of each read from parse_at
-        for (auto &sv : sub) sv.clear();
-        for (const Rec *r : fam)
-            if (r->subk >= 0) sub[r->subk].push_back(r);
-        // check_number_reads (:157-188)
-        int sampled = 0;
-        bool enough = true;
-        for (int k = 0; k < 4; ++k) {
-            const int n = (int)sub[k].size();
-            if (n < cfg.min_reads) { enough = false; break; }
-            if (n > cfg.max_reads) {
-                if (cfg.max_reads < 0) return stop(DCR_ERR_VALUE, "Sample larger than population or is negative");
-                if (gate_fn && !gate_open) {
-                    gate_open = true;
-                    if (gate_fn(gate_user, rng.mt, &rng.index) != 0 || rng.index < 0 || rng.index > 624)
-                    {
-                        g_err = "the state gate gave no generator state";
-                        return -1;
-                    }
-                }
-                rng.sample(n, cfg.max_reads, idx_tmp);
-                sample_calls.push_back(n);
-                sample_calls.push_back(cfg.max_reads);
-                std::vector<const Rec *> pick;
-                pick.reserve(idx_tmp.size());
-                for (int j : idx_tmp) pick.push_back(sub[k][(size_t)j]);
-                sub[k].swap(pick);
-                sampled |= 1 << k;
-            }
-        }
-        const int32_t t = b->n_tab++;
-        b->tab_sampled[t] = sampled;
-        b->tab_exc_cut[t] = b->n_side_exc;
-        b->tab_filt_cut[t] = b->n_side_filt;
-        b->tab_code[t] = put_name(code, l_code);
-        const int64_t code_off = b->tab_code[t];
-        if (!enough) {
-            // filtered family: its reads to _filteredfamilies.bam in input order (:1550-1551)
-            b->tab_kind[t] = DCR_FAM_FILTERED;
-            b->tab_proc[t] = -1;
-            for (const Rec *r : fam) {
-                std::memcpy(b->side_filt + b->n_side_filt, at(*r, 0), r->len);
-                b->n_side_filt += r->len;
-            }
-            ++filtered;
-            return 1;
-        }
-        // pack
-        const int32_t f = b->n_fam++;
-        b->tab_kind[t] = DCR_FAM_PROCESSED;
-        b->tab_proc[t] = f;
-        b->fam_tid[f] = r0.tid;
-        b->fam_code[f] = code_off;
-        int64_t mn[4], mx[4];
-        for (int k = 0; k < 4; ++k) {
-            int16_t eqx = 0;
-            mn[k] = mx[k] = 0;
-            bool first = true;
-            for (const Rec *rp : sub[k]) {
-                const Rec &r = *rp;
-                const int32_t i = b->n_reads++;
-                jobs.push_back(Job{r.off, b->n_bases, b->n_cigar, i});
-                b->n_bases += r.l_seq;
-                b->n_cigar += r.n_cig;
-                const int64_t end = r.end_kept;
-                if (first || r.pos < mn[k]) mn[k] = r.pos;
-                if (first || end > mx[k]) mx[k] = end;
-                first = false;
-                if (eqx < 0x7fff && r.eqx) ++eqx;
-            }
-            b->fam_eqx[4 * f + k] = (uint16_t)eqx;
-            b->sub_off[4 * f + k + 1] = b->n_reads;
-            const int64_t tt = (std::max<int64_t>(mx[k] - mn[k], 1) + 15) & ~(int64_t)15;
-            b->ss_col_off[4 * f + k + 1] = b->ss_col_off[4 * f + k] + tt;
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int a = 2 * j, c = 2 * j + 1;
-            int64_t tt = std::max(mx[a], mx[c]) - std::min(mn[a], mn[c]);
-            tt = (std::max<int64_t>(tt, 1) + 15) & ~(int64_t)15;
-            b->ds_col_off[2 * f + j + 1] = b->ds_col_off[2 * f + j] + tt;
-        }
-        b->ss_cols = b->ss_col_off[4 * f + 4];
-        b->ds_cols = b->ds_col_off[2 * f + 2];
-        // writer metadata: RX of the read0 of A1 and of B1 (:1367 via add_tags)
-        for (int j = 0; j < 2; ++j) {
-            const std::vector<const Rec *> &sv = sub[2 * j];
-            if (sv.empty()) b->fam_rx[2 * f + j] = put_name("", 0);
-            else b->fam_rx[2 * f + j] = put_name((const char *)at(*sv[0], sv[0]->o_rx), sv[0]->l_rx);
-        }
-        ++processed;
-        return 1;
-    }
-
     int64_t put_name(const char *s, size_t n) {
         const int64_t o = hb->n_names;
         std::memcpy(hb->names + o, s, n);
@@ -1898,7 +1821,6 @@ struct dcr_ingest {
         b->ss_col_off[0] = 0;
         b->ds_col_off[0] = 0;
         cap_err = 0;
-        if (jobs.capacity() < (size_t)b->cap_reads) jobs.reserve((size_t)b->cap_reads);
         // the queued families never reallocate under the packer (queue_family
         // drains them first when they would)
         if (tasks.capacity() < (size_t)b->cap_tab) tasks.reserve((size_t)b->cap_tab);
@@ -1910,7 +1832,6 @@ struct dcr_ingest {
         const double tw = prof.on ? IngestProf::now() : 0;
         int rc = walk();
         if (flush_tasks() < 0 && rc >= 0) rc = -1;
-        flush_jobs();
         if (prof.on) prof.walk_total += IngestProf::now() - tw;
         hb = nullptr;
         if (rc < 0) {
@@ -1967,7 +1888,6 @@ struct dcr_ingest {
                 if (c <= 0) return c;      // 0: batch full, the read stays unconsumed
                 fam.clear();
                 kick_tasks(false);
-                kick_jobs(false);
             }
             ++passed;
             ++records;

@@ -7,7 +7,7 @@
 // show up on the CPU; tests/test_stream_protocol.py compares the two hashes.
 // DCR_TEST_PASSES=n runs n ingests one after another in the process (the
 // bench's CLI passes share one inflater), printing a line per pass.
-//   usage: ingest_driver BAM HOOK [READS_PER_BATCH]
+//   usage: ingest_driver BAM HOOK [READS_PER_BATCH [MIN_READS [MAX_READS]]]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,7 +34,7 @@ std::vector<T> arr(size_t n) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s BAM HOOK [READS]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s BAM HOOK [READS [MIN_READS [MAX_READS]]]\n", argv[0]);
         return 2;
     }
     const int use_hook = std::atoi(argv[2]);
@@ -47,12 +47,18 @@ int main(int argc, char **argv) {
     const char *np = std::getenv("DCR_TEST_PASSES");
     const int passes = np && std::atoi(np) > 0 ? std::atoi(np) : 1;
     for (int pass = 0; pass < passes; ++pass) {
-    dcr_ingest_cfg cfg{20, 1, 100, 20, 0, 0};
+    dcr_ingest_cfg cfg{20, argc > 4 ? std::atoi(argv[4]) : 1, argc > 5 ? std::atoi(argv[5]) : 100, 20, 0, 0};
     dcr_ingest *ing = dcr_ingest_open(argv[1], &cfg);
     if (!ing) {
         std::fprintf(stderr, "open: %s\n", dcr_io_last_error());
         return 4;
     }
+    // a generator state to sample from (MT19937's init_genrand(5489)): the
+    // ingest's default, all zero, only ever draws 0
+    uint32_t mt[624];
+    mt[0] = 5489u;
+    for (uint32_t i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + i;
+    dcr_ingest_set_rng(ing, mt, 624);
     const int f = reads / 4 + 16, t = 2 * f;
     const int64_t nb = 160LL * reads, nn = 96LL * t + (1 << 16), ns = 64LL << 20;
     auto sub_off = arr<int32_t>(4 * f + 1), read_pos = arr<int32_t>(reads), seq_len = arr<int32_t>(reads),
