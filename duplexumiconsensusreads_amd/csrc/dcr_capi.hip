@@ -4,11 +4,20 @@
 // One context per GPU: its own HIP stream, device copy of the parameters, and
 // a grow-only workspace (reserve it once; the launch path never allocates,
 // so a caller may capture dcr_run_batch into a hipGraph).
+//
+// Every device buffer is laid out by one walk of a Plan (256-byte regions):
+// plan_workspace (the kernels' scratch), plan_io (a batch's inputs and both
+// strands' outputs) and plan_writer (the device record writer).  A caller
+// sizes with a null base, ensures the buffer, then walks again to fill the
+// pointers.  plan_io, upload_inputs and download_outputs loop over kInFields /
+// kOutFields, one row per array of dcr_batch / dcr_out in struct order.
+// dcr_submit and dcr_submit_write share slot_open (streams, the slot's events,
+// the busy check) and slot_run (wait for the upload, run, fetch the flag);
+// launch_strand<DUPLEX> is the kernel sequence of one strand.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstddef>
 #include <cstring>
 #include <cstdlib>
@@ -54,6 +63,182 @@ struct DevBuf {
 };
 
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
+
+// One walk over a buffer's regions.  take<T>(n) returns the next region, n
+// elements of T, and advances by its bytes (at least one) rounded up to 256.
+// With a null base it only sizes: off ends as the bytes the buffer needs.
+struct Plan {
+    char *base = nullptr;
+    size_t off = 0;
+    template <typename T> T *take(size_t n) {
+        T *p = base ? (T *)(base + off) : nullptr;
+        off = align_up(off + std::max<size_t>(n * sizeof(T), 1));
+        return p;
+    }
+};
+
+// The kernels' workspace for a batch of these sizes.
+void plan_workspace(const dcr_batch &s, Plan &p, dcr::Workspace &w) {
+    const size_t n_reads = (size_t)std::max<int64_t>(s.n_reads, 1);
+    const size_t cols = (size_t)std::max<int64_t>(std::max(s.ss_cols, s.ds_cols), 1);
+    const size_t n_rec = (size_t)std::max<int64_t>(4LL * s.n_fam, 1);
+    const size_t n_lay = (size_t)std::max<int64_t>(6LL * s.n_fam, 1);
+    w.info = p.take<dcr_read_info>(n_reads);
+    w.norm_cig = p.take<uint32_t>((size_t)std::max<int64_t>(s.n_cigar, 1));
+    w.cons = p.take<int32_t>(cols);
+    w.et = p.take<double>(cols);
+    w.insflag = p.take<uint8_t>((size_t)std::max<int64_t>(s.ss_cols, 1));
+    w.state = p.take<int4>(n_reads);
+    // one 64-byte block, reset as a whole per batch (dcr_run_batch)
+    dcr::Counters *ctr = (dcr::Counters *)p.take<char>(64);
+    w.stamps = p.take<unsigned long long>(64);
+    w.ovf = p.take<int>(n_rec);
+    w.xlist = p.take<int>(n_rec);
+    w.deep = p.take<int>(n_rec);
+    w.meta = p.take<dcr::RecMeta>(n_rec);
+    w.rmeta = p.take<uint2>(std::max<size_t>((size_t)s.n_reads, n_rec));
+    w.rows = p.take<uint4>(n_rec);
+    // insertion layouts: a row of kLayRow codes per single-strand read and per
+    // duplex input (two per duplex record)
+    w.lay_base = p.take<int>(n_lay);
+    w.lay_mask = p.take<uint64_t>(4 * n_lay);
+    w.lay = p.take<uint16_t>((size_t)dcr::kLayRow * (size_t)std::max<int64_t>(s.n_reads + 4LL * s.n_fam, 1));
+    if (!ctr) return;
+    w.err = &ctr->err;
+    w.ovf_count = ctr->ovf_count;
+    w.fast_count = ctr->fast_count;
+    w.xcount = ctr->xcount;
+    w.gen_next = ctr->gen_next;
+    w.deep_count = &ctr->deep_count;
+    w.lay_next = ctr->lay_next;
+}
+
+// The arrays of dcr_batch and dcr_out, in struct order: where the pointer
+// sits, its element size and which of the batch's sizes counts its elements.
+enum Count { kSubOff /* 4F + 1 */, kReads, kCigar, kBases, kDsOff /* 2F + 1 */, kRecords, kColumns };
+struct Field {
+    size_t at, elem;
+    Count count;
+};
+#define DCR_FIELD(S, m, count) {offsetof(S, m), sizeof(*((S *)nullptr)->m), count}
+constexpr Field kInFields[] = {
+    DCR_FIELD(dcr_batch, sub_off, kSubOff),   DCR_FIELD(dcr_batch, read_pos, kReads),
+    DCR_FIELD(dcr_batch, read_mapq, kReads),  DCR_FIELD(dcr_batch, seq_off, kReads),
+    DCR_FIELD(dcr_batch, seq_len, kReads),    DCR_FIELD(dcr_batch, cig_off, kReads),
+    DCR_FIELD(dcr_batch, cig_n, kReads),      DCR_FIELD(dcr_batch, cigar, kCigar),
+    DCR_FIELD(dcr_batch, bases, kBases),      DCR_FIELD(dcr_batch, quals, kBases),
+    DCR_FIELD(dcr_batch, ss_col_off, kSubOff), DCR_FIELD(dcr_batch, ds_col_off, kDsOff)};
+constexpr Field kOutFields[] = {
+    DCR_FIELD(dcr_out, status, kRecords), DCR_FIELD(dcr_out, pos, kRecords),   DCR_FIELD(dcr_out, mapq, kRecords),
+    DCR_FIELD(dcr_out, len, kRecords),    DCR_FIELD(dcr_out, n_cig, kRecords), DCR_FIELD(dcr_out, n_de, kRecords),
+    DCR_FIELD(dcr_out, D, kRecords),      DCR_FIELD(dcr_out, M, kRecords),     DCR_FIELD(dcr_out, E, kRecords),
+    DCR_FIELD(dcr_out, seq, kColumns),    DCR_FIELD(dcr_out, qual, kColumns),  DCR_FIELD(dcr_out, cigar, kColumns),
+    DCR_FIELD(dcr_out, d, kColumns),      DCR_FIELD(dcr_out, e, kColumns)};
+#undef DCR_FIELD
+// a pointer added to include/dcr.h without its row here does not compile
+template <size_t N> constexpr bool consecutive(const Field (&t)[N], size_t first) {
+    for (size_t i = 0; i < N; ++i)
+        if (t[i].at != first + i * sizeof(void *)) return false;
+    return true;
+}
+static_assert(sizeof(kInFields) / sizeof(Field) == 12 && sizeof(kOutFields) / sizeof(Field) == 14, "one row per array");
+static_assert(sizeof(dcr_batch) - offsetof(dcr_batch, sub_off) == 12 * sizeof(void *), "dcr_batch ends in 12 pointers");
+static_assert(sizeof(dcr_out) == 14 * sizeof(void *), "dcr_out is 14 pointers");
+static_assert(consecutive(kInFields, offsetof(dcr_batch, sub_off)) && consecutive(kOutFields, 0), "rows in struct order");
+
+void *field_ptr(const void *obj, const Field &f) {
+    void *p;
+    std::memcpy(&p, (const char *)obj + f.at, sizeof(p));
+    return p;
+}
+void set_field_ptr(void *obj, const Field &f, void *p) { std::memcpy((char *)obj + f.at, &p, sizeof(p)); }
+
+// elements of an input array of batch h
+size_t in_count(const dcr_batch *h, Count k) {
+    const int64_t n[] = {4 * (int64_t)h->n_fam + 1, h->n_reads, h->n_cigar, h->n_bases, 2 * (int64_t)h->n_fam + 1};
+    return (size_t)n[k];
+}
+
+// Device layout of one batch's inputs and outputs in a single buffer; with a
+// base it also fills the device views db (inputs) and dout[0..1]
+// (single-strand, duplex outputs).
+void plan_io(const dcr_batch *h, Plan &p, dcr_batch *db, dcr_out dout[2]) {
+    if (p.base) *db = *h;
+    for (const Field &f : kInFields) {
+        char *r = p.take<char>(f.elem * in_count(h, f.count));
+        if (p.base) set_field_ptr(db, f, r);
+    }
+    const int64_t nrec[2] = {4 * (int64_t)h->n_fam, 2 * (int64_t)h->n_fam};
+    const int64_t ncol[2] = {h->ss_cols, h->ds_cols};
+    for (int k = 0; k < 2; ++k)
+        for (const Field &f : kOutFields) {
+            char *r = p.take<char>(f.elem * (size_t)(f.count == kRecords ? nrec[k] : ncol[k]));
+            if (p.base) set_field_ptr(&dout[k], f, r);
+        }
+}
+
+size_t io_bytes(const dcr_batch *h) {
+    Plan sz;
+    plan_io(h, sz, nullptr, nullptr);
+    return sz.off;
+}
+
+// the host batch's inputs -> device views (async on stream s)
+hipError_t upload_inputs(const dcr_batch *h, const dcr_batch &db, hipStream_t s) {
+    for (const Field &f : kInFields)
+        if (const size_t bytes = f.elem * in_count(h, f.count)) {
+            hipError_t e = hipMemcpyAsync(field_ptr(&db, f), field_ptr(h, f), bytes, hipMemcpyHostToDevice, s);
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
+
+// device outputs -> the host dcr_out arrays that are not NULL (async on stream s)
+hipError_t download_outputs(const dcr_out *dev, dcr_out *host, int64_t R, int64_t C, hipStream_t s) {
+    for (const Field &f : kOutFields) {
+        const size_t bytes = f.elem * (size_t)(f.count == kRecords ? R : C);
+        if (field_ptr(host, f) && bytes) {
+            hipError_t e = hipMemcpyAsync(field_ptr(host, f), field_ptr(dev, f), bytes, hipMemcpyDeviceToHost, s);
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+// The device record writer's buffer: the metadata uploaded with the batch,
+// the per-record sizes and offsets, the record stream and the BGZF blocks.
+struct WriterBufs {
+    char *names;
+    int64_t *fam_code, *fam_rx;
+    int32_t *fam_tid, *fam_fail, *ds_len;
+    int64_t *rec_size, *rec_off, *scan;
+    uint8_t *stream, *slots;
+    int64_t *bsz, *boff;    // block sizes (+ the scan's total, then k_deflate's block counter), offsets
+    uint8_t *comp;
+    int64_t *tot;
+    uint32_t *tok;
+};
+
+// F families, n_names bytes of names, a record stream of at most B bytes in
+// at most nbm blocks, gd k_deflate workgroups
+void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w) {
+    w.names = p.take<char>((size_t)n_names + 1);
+    w.fam_code = p.take<int64_t>((size_t)F);
+    w.fam_rx = p.take<int64_t>(2 * (size_t)F);
+    w.fam_tid = p.take<int32_t>((size_t)F);
+    w.fam_fail = p.take<int32_t>((size_t)F);
+    w.ds_len = p.take<int32_t>(2 * (size_t)F);
+    w.rec_size = p.take<int64_t>((size_t)(2 * F + 1));
+    w.rec_off = p.take<int64_t>((size_t)(2 * F + 1));
+    w.scan = (int64_t *)p.take<char>(std::max(dcrw::scan_tmp_bytes((int)(2 * F + 1)), dcrw::scan_tmp_bytes((int)(nbm + 1))));
+    w.stream = p.take<uint8_t>((size_t)B);
+    w.slots = p.take<uint8_t>((size_t)nbm * dfl::kSlot);
+    w.bsz = p.take<int64_t>((size_t)(nbm + 2));
+    w.boff = p.take<int64_t>((size_t)(nbm + 1));
+    w.comp = p.take<uint8_t>((size_t)nbm * dfl::kSlot);
+    w.tot = p.take<int64_t>(4);
+    w.tok = p.take<uint32_t>((size_t)gd * dfl::kTokWords);
+}
 }  // namespace
 
 int dcr::set_error(int code, const std::string &msg) { return fail(code, msg); }
@@ -86,7 +271,7 @@ struct dcr_ctx {
     struct Slot {
         DevBuf buf;
         DevBuf wbuf;              // device record writer: metadata, record stream, BGZF blocks
-        int64_t *d_rec_off = nullptr, *d_comp_n = nullptr;
+        int64_t *d_rec_off = nullptr;
         uint8_t *d_stream = nullptr, *d_comp = nullptr;
         int64_t n_fam = 0;
         bool writer = false;
@@ -113,7 +298,6 @@ struct dcr_ctx {
     // the kernels only records that large can need (k_prep_big > 64 reads,
     // k_decide_deep >= kDeepReads) are not launched for batches without them
     int max_r_hint = -1;
-    int rm_waves = dcr::kRecmetaWaves;   // k_recmeta block size for light records (DCR_RM_WAVES: A/B runs)
     uint16_t *d_llr16 = nullptr;   // device [128]
     uint16_t *d_llr8 = nullptr;    // device [128]
     uint32_t *d_r2tab = nullptr;   // device [dcr::kR2Entries]: two-read column outcomes (EXACT pass)
@@ -244,6 +428,122 @@ static int upload_fast(dcr_ctx *c, const dcr_params *params) {
     return DCR_OK;
 }
 
+// the fast kernel's arguments for one strand of a batch
+static dcr::FastArgs fast_args(const dcr_ctx *c, bool duplex, const dcr_batch *in, const dcr_out *ss,
+                               const dcr_out *ds) {
+    dcr::FastArgs f{};
+    f.gb = duplex ? ss->seq : in->bases;
+    f.gq = duplex ? ss->qual : in->quals;
+    f.nbytes = duplex ? in->ss_cols : in->n_bases;
+    f.meta = c->w.meta;
+    f.rows = c->w.rows;
+    f.rmeta = c->w.rmeta;
+    f.fast_count = c->w.fast_count + (duplex ? 1 : 0);
+    f.info = c->w.info;
+    f.norm_cig = c->w.norm_cig;
+    f.cig_off = in->cig_off;
+    f.ovf = c->w.ovf;
+    f.ovf_count = c->w.ovf_count + (duplex ? 1 : 0);
+    f.xlist = c->w.xlist;
+    f.xcount = c->w.xcount + (duplex ? 1 : 0);
+    f.O = duplex ? *ds : *ss;
+    f.P = c->d_params;
+    f.stamps = c->w.stamps;
+    f.kq = c->fast_kq;
+    f.kqlo = c->fast_kqlo;
+    f.maxq = c->fast_maxq;
+    f.t16 = c->fast_t16;
+    f.r_safe = c->fast_r_safe;
+    f.minbq = duplex ? -1 : c->host_params.min_base_quality;
+    f.lo_check = duplex || c->host_params.min_base_quality < c->fast_qlo;
+    f.llr16 = c->d_llr16;
+    f.llr8 = c->d_llr8;
+    f.r2tab = c->d_r2tab;
+    f.t8 = c->fast_t8;
+    f.narrow = c->fast_narrow;
+    f.e1000 = c->d_e1000;
+    {
+        // record-scalar stores at 32-bit offsets from the lowest array
+        // (k_consensus_fast): every array + its largest index within 4 GiB
+        const dcr_out &O = f.O;
+        const int64_t nrec = (duplex ? 2 : 4) * in->n_fam, ncol = duplex ? in->ds_cols : in->ss_cols;
+        const uint8_t *p[10] = {(const uint8_t *)O.pos, (const uint8_t *)O.mapq, (const uint8_t *)O.len,
+                                (const uint8_t *)O.n_cig, (const uint8_t *)O.n_de, (const uint8_t *)O.D,
+                                (const uint8_t *)O.M, (const uint8_t *)O.E, (const uint8_t *)O.E + 4,
+                                (const uint8_t *)O.cigar};
+        const uint8_t *lo = p[0];
+        for (int k = 1; k < 10; ++k) lo = std::min(lo, p[k]);
+        bool ok = lo != nullptr;
+        for (int k = 0; k < 10 && ok; ++k) {
+            const uint64_t reach = (uint64_t)(p[k] - lo) + (k == 9 ? 4 * (uint64_t)ncol : (k == 7 || k == 8 ? 8 : 4) * (uint64_t)nrec);
+            ok = p[k] != nullptr && reach < 0xFFFFFFF0ull;
+            f.sofs[k] = (uint32_t)(p[k] - lo);
+        }
+        f.sbase = ok ? (uint8_t *)lo : nullptr;
+    }
+    f.want_info = (c->options & DCR_OPT_READ_INFO) ? 1 : 0;
+    f.direct_r = duplex ? 0 : c->direct_r;
+    return f;
+}
+
+// One strand of a batch: k_recmeta classifies every record (fast list /
+// general list / status written), then the fast kernel (8 records per wave)
+// drains the fast list and the persistent general kernel the rest
+// (insertions, > 64 reads, wide layouts).  Events ev[0..3] of the strand.
+template <bool DUPLEX>
+static int launch_strand(dcr_ctx *c, dcr::Args &a, const dcr_batch *in, const dcr_out *ss, const dcr_out *ds) {
+    a.n_rec = (DUPLEX ? 2LL : 4LL) * in->n_fam;
+    const int64_t n_rec = a.n_rec;
+    const dcr::FastArgs fa = fast_args(c, DUPLEX, in, ss, ds);
+    auto grid_for = [&](unsigned cap) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rec + 3) / 4, cap)); };
+    // k_recmeta: 64 records per wave, or fewer when the reads per record
+    // exceed 16 on average (about 1,024 reads per wave)
+    int rpw = 64;
+    if (!DUPLEX && n_rec > 0) {
+        const int64_t avg = (int64_t)in->n_reads / n_rec;
+        while (rpw > 1 && (int64_t)rpw * avg > 1024) rpw >>= 1;
+    }
+    a.rpw = rpw;
+    const int rm_waves = rpw == 64 ? dcr::kRecmetaWaves : 4;    // heavy records: small blocks
+    const int64_t rpb = (int64_t)rm_waves * rpw;                // records per k_recmeta block
+    const unsigned nb = (unsigned)((n_rec + rpb - 1) / rpb);
+    hipEvent_t *ev = c->ev + (DUPLEX ? 5 : 1);
+    // persistent fast kernel: the resident blocks (16 waves each), at least
+    // ~8 records per wave
+    const unsigned gf = (unsigned)std::max<int64_t>(
+        1, std::min<int64_t>((n_rec + 127) / 128, (int64_t)c->fast_blocks[DUPLEX ? 1 : 0] * c->n_cu));
+    // the exact queue is filled by the common kernel; its length is only
+    // known on the device, so the exact kernel gets the resident grid
+    const unsigned gx = (unsigned)((int64_t)c->fast_blocks[DUPLEX ? 3 : 2] * c->n_cu);
+    hipLaunchKernelGGL(dcr::k_recmeta<DUPLEX>, dim3(nb), dim3(rm_waves * dcr::kWave), dcr::recmeta_lds_bytes(rm_waves),
+                       c->stream, a);
+    if constexpr (!DUPLEX)
+        if (c->max_r_hint < 0 || c->max_r_hint > dcr::kWave)
+            hipLaunchKernelGGL(dcr::k_prep_big, dim3(grid_for(2048)), dim3(256), 0, c->stream, a);
+    HIP_TRY(hipEventRecord(ev[0], c->stream));
+    hipLaunchKernelGGL((dcr::k_consensus_fast<DUPLEX, false>), dim3(gf), dim3(dcr::kFastBlock), 0, c->stream, fa);
+    // k_fast_rows: one lane per fast-list entry (the list is at most n_rec long)
+    hipLaunchKernelGGL(dcr::k_fast_rows, dim3((unsigned)std::max<int64_t>(1, (n_rec + 255) / 256)), dim3(256), 0,
+                       c->stream, fa);
+    HIP_TRY(hipEventRecord(ev[1], c->stream));
+    hipLaunchKernelGGL((dcr::k_consensus_fast<DUPLEX, true>), dim3(gx), dim3(dcr::kFastBlock), 0, c->stream, fa);
+    HIP_TRY(hipEventRecord(ev[2], c->stream));
+    hipLaunchKernelGGL(dcr::k_decide<DUPLEX>, dim3(grid_for(2048)), dim3(256), 0, c->stream, a);
+    // k_decide_deep only when the batch may hold a deep record (its 66 KB
+    // blocks wait for room beside the inflate waves in the whole-node
+    // pipeline even when they find none: up to 7 ms per C2 pass, profiles/r06g)
+    if constexpr (!DUPLEX)
+        if (c->max_r_hint < 0 || c->max_r_hint >= dcr::kDeepReads)
+            hipLaunchKernelGGL(dcr::k_decide_deep, dim3(2 * c->n_cu), dim3(dcr::kDeepWaves * dcr::kWave), 0, c->stream, a);
+    // after k_decide_deep: it reads the general list's entries, which
+    // k_ins_layout marks decided (bit 31) for the records it decides
+    hipLaunchKernelGGL(dcr::k_ins_layout<DUPLEX>, dim3(grid_for(2048)), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(dcr::k_consensus_general<DUPLEX>, dim3(grid_for(1024)), dim3(256), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[3], c->stream));
+    return DCR_OK;
+}
+
 extern "C" {
 
 int dcr_abi_version(void) { return DCR_ABI_VERSION; }
@@ -275,10 +575,6 @@ dcr_ctx *dcr_create(int device, const dcr_params *params) {
     dcr_ctx *c = new dcr_ctx();
     c->device = device;
     if (const char *e = std::getenv("DCR_EXACT_DIRECT_R")) c->direct_r = std::atoi(e);   // A/B runs
-    if (const char *e = std::getenv("DCR_RM_WAVES")) {                                  // A/B runs
-        const int w = std::atoi(e);
-        if (w == 4 || w == 8 || w == 16) c->rm_waves = w;
-    }
     if (hipSetDevice(device) != hipSuccess ||
         hi_prio_stream(&c->stream) != hipSuccess ||
         hipMalloc(&c->d_params, sizeof(dcr_params)) != hipSuccess ||
@@ -374,57 +670,15 @@ int dcr_set_options(dcr_ctx *c, int flags) {
 int dcr_reserve(dcr_ctx *c, const dcr_batch *s) {
     if (!c || !s) return fail(DCR_EARG, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
-    const int64_t cols = std::max(s->ss_cols, s->ds_cols);
-    size_t o = 0;
-    const size_t o_info = o; o = align_up(o + sizeof(dcr_read_info) * (size_t)std::max<int64_t>(s->n_reads, 1));
-    const size_t o_cig = o;  o = align_up(o + sizeof(uint32_t) * (size_t)std::max<int64_t>(s->n_cigar, 1));
-    const size_t o_cons = o; o = align_up(o + sizeof(int32_t) * (size_t)std::max<int64_t>(cols, 1));
-    const size_t o_et = o;   o = align_up(o + sizeof(double) * (size_t)std::max<int64_t>(cols, 1));
-    const size_t o_ins = o;  o = align_up(o + (size_t)std::max<int64_t>(s->ss_cols, 1));
-    const size_t o_st = o;   o = align_up(o + sizeof(int4) * (size_t)std::max<int64_t>(s->n_reads, 1));
-    const size_t o_err = o;  o = align_up(o + 64);
-    const size_t o_stamp = o; o = align_up(o + 64 * sizeof(unsigned long long));
-    const size_t n_rec = (size_t)std::max<int64_t>(4LL * s->n_fam, 1);
-    const size_t o_ovf = o;  o = align_up(o + sizeof(int) * n_rec);
-    const size_t o_xl = o;   o = align_up(o + sizeof(int) * n_rec);
-    const size_t o_deep = o; o = align_up(o + sizeof(int) * n_rec);
-    const size_t o_meta = o; o = align_up(o + sizeof(dcr::RecMeta) * n_rec);
-    const size_t o_rm = o;   o = align_up(o + sizeof(uint2) * std::max<size_t>((size_t)s->n_reads, n_rec));
-    const size_t o_rows = o; o = align_up(o + sizeof(uint4) * n_rec);
-    // insertion layouts: a row of kLayRow codes per single-strand read and per
-    // duplex input (two per duplex record)
-    const size_t o_lb = o;   o = align_up(o + sizeof(int) * (size_t)std::max<int64_t>(6LL * s->n_fam, 1));
-    const size_t o_lm = o;   o = align_up(o + 4 * sizeof(uint64_t) * (size_t)std::max<int64_t>(6LL * s->n_fam, 1));
-    const size_t o_lay = o;
-    o = align_up(o + sizeof(uint16_t) * (size_t)dcr::kLayRow * (size_t)std::max<int64_t>(s->n_reads + 4LL * s->n_fam, 1));
-    if (o > c->ws.cap) {
+    Plan sz;
+    dcr::Workspace unused;
+    plan_workspace(*s, sz, unused);
+    if (sz.off > c->ws.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(c->ws.ensure(o + o / 8));
+        HIP_TRY(c->ws.ensure(sz.off + sz.off / 8));
     }
-    char *b = (char *)c->ws.p;
-    c->w.info = (dcr_read_info *)(b + o_info);
-    c->w.norm_cig = (uint32_t *)(b + o_cig);
-    c->w.cons = (int32_t *)(b + o_cons);
-    c->w.et = (double *)(b + o_et);
-    c->w.insflag = (uint8_t *)(b + o_ins);
-    c->w.state = (int4 *)(b + o_st);
-    c->w.err = (int *)(b + o_err);
-    c->w.ovf_count = (int *)(b + o_err) + 1;     // err, ovf_count[2], fast_count[2], xcount[2], gen_next[2]: one block
-    c->w.fast_count = (int *)(b + o_err) + 3;
-    c->w.xcount = (int *)(b + o_err) + 5;
-    c->w.gen_next = (int *)(b + o_err) + 7;      // [2], in the same block: reset with it per batch
-    c->w.deep_count = (int *)(b + o_err) + 9;    // [1], likewise
-    c->w.lay_next = (int *)(b + o_err) + 10;     // [2], likewise
-    c->w.lay_base = (int *)(b + o_lb);
-    c->w.lay_mask = (uint64_t *)(b + o_lm);
-    c->w.lay = (uint16_t *)(b + o_lay);
-    c->w.deep = (int *)(b + o_deep);
-    c->w.xlist = (int *)(b + o_xl);
-    c->w.stamps = (unsigned long long *)(b + o_stamp);
-    c->w.ovf = (int *)(b + o_ovf);
-    c->w.meta = (dcr::RecMeta *)(b + o_meta);
-    c->w.rmeta = (uint2 *)(b + o_rm);
-    c->w.rows = (uint4 *)(b + o_rows);
+    Plan p{(char *)c->ws.p};
+    plan_workspace(*s, p, c->w);
     return DCR_OK;
 }
 
@@ -434,7 +688,7 @@ int dcr_run_batch(dcr_ctx *c, const dcr_batch *in, dcr_out *ss, dcr_out *ds) {
     int rc = dcr_reserve(c, in);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemsetAsync(c->w.err, 0, 64, c->stream));
+    HIP_TRY(hipMemsetAsync(c->w.err, 0, 64, c->stream));   // dcr::Counters
     c->last_reads = in->n_reads;
     // per-read preprocessing (:191-325) is fused: k_recmeta<ss> analyses the
     // clips and fully preprocesses the reads of records the fast kernel does
@@ -449,137 +703,9 @@ int dcr_run_batch(dcr_ctx *c, const dcr_batch *in, dcr_out *ss, dcr_out *ds) {
     a.fast_ok = c->fast_ok;
     a.t16 = c->wide_ok ? c->fast_t16 : -1;     // -1: no decision pass
     a.wtab = c->d_wtab;
-    // per strand: k_recmeta classifies every record (fast list / general list /
-    // status written), then the fast kernel (8 records per wave) drains the fast list and
-    // the persistent general kernel the rest (insertions, > 64 reads, wide layouts)
-    auto grid_for = [&](int64_t n_rec, unsigned cap) {
-        return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rec + 3) / 4, cap));
-    };
-    // persistent fast kernel: the resident blocks (16 waves each), at least
-    // ~8 records per wave
-    auto fast_grid = [&](int64_t n_rec, int k) {
-        return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rec + 127) / 128, (int64_t)c->fast_blocks[k] * c->n_cu));
-    };
-    // k_fast_rows: one lane per fast-list entry (the list is at most n_rec long)
-    auto rows_grid = [&](int64_t n_rec) { return (unsigned)std::max<int64_t>(1, (n_rec + 255) / 256); };
-    auto fast_args = [&](bool duplex) {
-        dcr::FastArgs f{};
-        f.gb = duplex ? ss->seq : in->bases;
-        f.gq = duplex ? ss->qual : in->quals;
-        f.nbytes = duplex ? in->ss_cols : in->n_bases;
-        f.meta = c->w.meta;
-        f.rows = c->w.rows;
-        f.rmeta = c->w.rmeta;
-        f.fast_count = c->w.fast_count + (duplex ? 1 : 0);
-        f.info = c->w.info;
-        f.norm_cig = c->w.norm_cig;
-        f.cig_off = in->cig_off;
-        f.ovf = c->w.ovf;
-        f.ovf_count = c->w.ovf_count + (duplex ? 1 : 0);
-        f.xlist = c->w.xlist;
-        f.xcount = c->w.xcount + (duplex ? 1 : 0);
-        f.O = duplex ? *ds : *ss;
-        f.P = c->d_params;
-        f.stamps = c->w.stamps;
-        f.kq = c->fast_kq;
-        f.kqlo = c->fast_kqlo;
-        f.maxq = c->fast_maxq;
-        f.t16 = c->fast_t16;
-        f.r_safe = c->fast_r_safe;
-        f.minbq = duplex ? -1 : c->host_params.min_base_quality;
-        f.lo_check = duplex || c->host_params.min_base_quality < c->fast_qlo;
-        f.llr16 = c->d_llr16;
-        f.llr8 = c->d_llr8;
-        f.r2tab = c->d_r2tab;
-        f.t8 = c->fast_t8;
-        f.narrow = c->fast_narrow;
-        f.e1000 = c->d_e1000;
-        {
-            // record-scalar stores at 32-bit offsets from the lowest array
-            // (k_consensus_fast): every array + its largest index within 4 GiB
-            const dcr_out &O = f.O;
-            const int64_t nrec = (duplex ? 2 : 4) * in->n_fam, ncol = duplex ? in->ds_cols : in->ss_cols;
-            const uint8_t *p[10] = {(const uint8_t *)O.pos, (const uint8_t *)O.mapq, (const uint8_t *)O.len,
-                                    (const uint8_t *)O.n_cig, (const uint8_t *)O.n_de, (const uint8_t *)O.D,
-                                    (const uint8_t *)O.M, (const uint8_t *)O.E, (const uint8_t *)O.E + 4,
-                                    (const uint8_t *)O.cigar};
-            const uint8_t *lo = p[0];
-            for (int k = 1; k < 10; ++k) lo = std::min(lo, p[k]);
-            bool ok = lo != nullptr;
-            for (int k = 0; k < 10 && ok; ++k) {
-                const uint64_t reach = (uint64_t)(p[k] - lo) + (k == 9 ? 4 * (uint64_t)ncol : (k == 7 || k == 8 ? 8 : 4) * (uint64_t)nrec);
-                ok = p[k] != nullptr && reach < 0xFFFFFFF0ull;
-                f.sofs[k] = (uint32_t)(p[k] - lo);
-            }
-            f.sbase = ok ? (uint8_t *)lo : nullptr;
-        }
-        f.want_info = (c->options & DCR_OPT_READ_INFO) ? 1 : 0;
-        f.direct_r = duplex ? 0 : c->direct_r;
-        return f;
-    };
-    auto strand = [&](bool duplex) -> int {
-        a.n_rec = (duplex ? 2LL : 4LL) * in->n_fam;
-        const dcr::FastArgs fa = fast_args(duplex);
-        // k_recmeta: 64 records per wave, or fewer when the reads per record
-        // exceed 16 on average (about 1,024 reads per wave)
-        int rpw = 64;
-        if (!duplex && a.n_rec > 0) {
-            const int64_t avg = (int64_t)in->n_reads / a.n_rec;
-            while (rpw > 1 && (int64_t)rpw * avg > 1024) rpw >>= 1;
-        }
-        a.rpw = rpw;
-        const int rm_waves = rpw == 64 ? c->rm_waves : 4;           // heavy records: small blocks
-        const int64_t rpb = (int64_t)rm_waves * rpw;                // records per k_recmeta block
-        const unsigned nb = (unsigned)((a.n_rec + rpb - 1) / rpb);
-        const size_t rm_lds = dcr::recmeta_lds_bytes(rm_waves);
-        hipEvent_t *ev = c->ev + (duplex ? 5 : 1);
-        // the exact queue is filled by the common kernel; its length is only
-        // known on the device, so the exact kernel gets the resident grid
-        const unsigned gx = (unsigned)((int64_t)c->fast_blocks[duplex ? 3 : 2] * c->n_cu);
-        if (duplex) {
-            hipLaunchKernelGGL(dcr::k_recmeta<true>, dim3(nb), dim3(rm_waves * dcr::kWave), rm_lds, c->stream, a);
-            HIP_TRY(hipEventRecord(ev[0], c->stream));
-            hipLaunchKernelGGL((dcr::k_consensus_fast<true, false>), dim3(fast_grid(a.n_rec, 1)), dim3(dcr::kFastBlock),
-                               0, c->stream, fa);
-            hipLaunchKernelGGL(dcr::k_fast_rows, dim3(rows_grid(a.n_rec)), dim3(256), 0, c->stream, fa);
-            HIP_TRY(hipEventRecord(ev[1], c->stream));
-            hipLaunchKernelGGL((dcr::k_consensus_fast<true, true>), dim3(gx), dim3(dcr::kFastBlock), 0, c->stream, fa);
-            HIP_TRY(hipEventRecord(ev[2], c->stream));
-            hipLaunchKernelGGL(dcr::k_decide<true>, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
-            hipLaunchKernelGGL(dcr::k_ins_layout<true>, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
-            hipLaunchKernelGGL(dcr::k_consensus_general<true>, dim3(grid_for(a.n_rec, 1024)), dim3(256), 0,
-                               c->stream, a);
-        } else {
-            hipLaunchKernelGGL(dcr::k_recmeta<false>, dim3(nb), dim3(rm_waves * dcr::kWave), rm_lds, c->stream, a);
-            if (c->max_r_hint < 0 || c->max_r_hint > dcr::kWave)
-                hipLaunchKernelGGL(dcr::k_prep_big, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
-            HIP_TRY(hipEventRecord(ev[0], c->stream));
-            hipLaunchKernelGGL((dcr::k_consensus_fast<false, false>), dim3(fast_grid(a.n_rec, 0)),
-                               dim3(dcr::kFastBlock), 0, c->stream, fa);
-            hipLaunchKernelGGL(dcr::k_fast_rows, dim3(rows_grid(a.n_rec)), dim3(256), 0, c->stream, fa);
-            HIP_TRY(hipEventRecord(ev[1], c->stream));
-            hipLaunchKernelGGL((dcr::k_consensus_fast<false, true>), dim3(gx), dim3(dcr::kFastBlock), 0, c->stream, fa);
-            HIP_TRY(hipEventRecord(ev[2], c->stream));
-            hipLaunchKernelGGL(dcr::k_decide<false>, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
-            // (its 66 KB blocks wait for room beside the inflate waves in the
-            // whole-node pipeline even when they find no deep record: up to
-            // 7 ms per C2 pass, profiles/r06g)
-            if (c->max_r_hint < 0 || c->max_r_hint >= dcr::kDeepReads)
-                hipLaunchKernelGGL(dcr::k_decide_deep, dim3(2 * c->n_cu), dim3(dcr::kDeepWaves * dcr::kWave), 0, c->stream,
-                                   a);
-            // after k_decide_deep: it reads the general list's entries, which
-            // k_ins_layout marks decided (bit 31) for the records it decides
-            hipLaunchKernelGGL(dcr::k_ins_layout<false>, dim3(grid_for(a.n_rec, 2048)), dim3(256), 0, c->stream, a);
-            hipLaunchKernelGGL(dcr::k_consensus_general<false>, dim3(grid_for(a.n_rec, 1024)), dim3(256), 0,
-                               c->stream, a);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[3], c->stream));
-        return DCR_OK;
-    };
     if (in->n_fam > 0) {
-        if ((rc = strand(false))) return rc;
-        if ((rc = strand(true))) return rc;
+        if ((rc = launch_strand<false>(c, a, in, ss, ds))) return rc;
+        if ((rc = launch_strand<true>(c, a, in, ss, ds))) return rc;
     } else {
         for (int k = 1; k <= DCR_N_KERNEL_TIMES; ++k) HIP_TRY(hipEventRecord(c->ev[k], c->stream));
     }
@@ -648,125 +774,19 @@ int dcr_read_info_host(dcr_ctx *c, dcr_read_info *out, int64_t n) {
     return DCR_OK;
 }
 
-// Device layout of one batch's inputs and outputs in a single buffer:
-// returns the bytes needed; with base != nullptr also fills the device
-// views db (inputs) and dout[0..1] (single-strand, duplex outputs).
-static size_t plan_io(const dcr_batch *h, char *base, dcr_batch *db, dcr_out dout[2]) {
-    const int64_t F = h->n_fam, n = h->n_reads;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1)); return o; };
-    const size_t o_sub = take(sizeof(int32_t) * (4 * F + 1));
-    const size_t o_pos = take(sizeof(int32_t) * n);
-    const size_t o_mq = take(n);
-    const size_t o_so = take(sizeof(int64_t) * n);
-    const size_t o_sl = take(sizeof(int32_t) * n);
-    const size_t o_co = take(sizeof(int32_t) * n);
-    const size_t o_cn = take(sizeof(int32_t) * n);
-    const size_t o_cg = take(sizeof(uint32_t) * h->n_cigar);
-    const size_t o_b = take(h->n_bases);
-    const size_t o_q = take(h->n_bases);
-    const size_t o_sc = take(sizeof(int64_t) * (4 * F + 1));
-    const size_t o_dc = take(sizeof(int64_t) * (2 * F + 1));
-    size_t oo[2][14];
-    const int64_t nrec[2] = {4 * F, 2 * F};
-    const int64_t ncol[2] = {h->ss_cols, h->ds_cols};
-    for (int k = 0; k < 2; ++k) {
-        oo[k][0] = take(nrec[k]);
-        for (int j = 1; j <= 7; ++j) oo[k][j] = take(sizeof(int32_t) * nrec[k]);
-        oo[k][8] = take(sizeof(double) * nrec[k]);
-        oo[k][9] = take(ncol[k]);
-        oo[k][10] = take(ncol[k]);
-        oo[k][11] = take(sizeof(uint32_t) * ncol[k]);
-        oo[k][12] = take(sizeof(uint16_t) * ncol[k]);
-        oo[k][13] = take(sizeof(uint16_t) * ncol[k]);
-    }
-    if (!base) return off;
-    char *d = base;
-    *db = *h;
-    db->sub_off = (const int32_t *)(d + o_sub);
-    db->read_pos = (const int32_t *)(d + o_pos);
-    db->read_mapq = (const uint8_t *)(d + o_mq);
-    db->seq_off = (const int64_t *)(d + o_so);
-    db->seq_len = (const int32_t *)(d + o_sl);
-    db->cig_off = (const int32_t *)(d + o_co);
-    db->cig_n = (const int32_t *)(d + o_cn);
-    db->cigar = (const uint32_t *)(d + o_cg);
-    db->bases = (const uint8_t *)(d + o_b);
-    db->quals = (const uint8_t *)(d + o_q);
-    db->ss_col_off = (const int64_t *)(d + o_sc);
-    db->ds_col_off = (const int64_t *)(d + o_dc);
-    for (int k = 0; k < 2; ++k) {
-        dout[k].status = (uint8_t *)(d + oo[k][0]);
-        dout[k].pos = (int32_t *)(d + oo[k][1]);
-        dout[k].mapq = (int32_t *)(d + oo[k][2]);
-        dout[k].len = (int32_t *)(d + oo[k][3]);
-        dout[k].n_cig = (int32_t *)(d + oo[k][4]);
-        dout[k].n_de = (int32_t *)(d + oo[k][5]);
-        dout[k].D = (int32_t *)(d + oo[k][6]);
-        dout[k].M = (int32_t *)(d + oo[k][7]);
-        dout[k].E = (double *)(d + oo[k][8]);
-        dout[k].seq = (uint8_t *)(d + oo[k][9]);
-        dout[k].qual = (uint8_t *)(d + oo[k][10]);
-        dout[k].cigar = (uint32_t *)(d + oo[k][11]);
-        dout[k].d = (uint16_t *)(d + oo[k][12]);
-        dout[k].e = (uint16_t *)(d + oo[k][13]);
-    }
-    return off;
-}
-
-// the host batch's inputs -> device views (async on stream s)
-static hipError_t upload_inputs(const dcr_batch *h, const dcr_batch &db, hipStream_t s) {
-    const int64_t F = h->n_fam, n = h->n_reads;
-    struct P { void *dst; const void *src; size_t bytes; } ps[12] = {
-        {(void *)db.sub_off, h->sub_off, sizeof(int32_t) * (4 * F + 1)},
-        {(void *)db.read_pos, h->read_pos, sizeof(int32_t) * n},
-        {(void *)db.read_mapq, h->read_mapq, (size_t)n},
-        {(void *)db.seq_off, h->seq_off, sizeof(int64_t) * n},
-        {(void *)db.seq_len, h->seq_len, sizeof(int32_t) * n},
-        {(void *)db.cig_off, h->cig_off, sizeof(int32_t) * n},
-        {(void *)db.cig_n, h->cig_n, sizeof(int32_t) * n},
-        {(void *)db.cigar, h->cigar, sizeof(uint32_t) * h->n_cigar},
-        {(void *)db.bases, h->bases, (size_t)h->n_bases},
-        {(void *)db.quals, h->quals, (size_t)h->n_bases},
-        {(void *)db.ss_col_off, h->ss_col_off, sizeof(int64_t) * (4 * F + 1)},
-        {(void *)db.ds_col_off, h->ds_col_off, sizeof(int64_t) * (2 * F + 1)}};
-    for (auto &p : ps)
-        if (p.bytes) {
-            hipError_t e = hipMemcpyAsync(p.dst, p.src, p.bytes, hipMemcpyHostToDevice, s);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
-
-// device outputs -> the host dcr_out arrays that are not NULL (async on stream s)
-static hipError_t download_outputs(const dcr_out *dev, dcr_out *host, int64_t R, int64_t C, hipStream_t s) {
-    struct P { void *dst; const void *src; size_t bytes; } ps[14] = {
-        {host->status, dev->status, (size_t)R}, {host->pos, dev->pos, 4 * (size_t)R},
-        {host->mapq, dev->mapq, 4 * (size_t)R}, {host->len, dev->len, 4 * (size_t)R},
-        {host->n_cig, dev->n_cig, 4 * (size_t)R}, {host->n_de, dev->n_de, 4 * (size_t)R},
-        {host->D, dev->D, 4 * (size_t)R}, {host->M, dev->M, 4 * (size_t)R}, {host->E, dev->E, 8 * (size_t)R},
-        {host->seq, dev->seq, (size_t)C}, {host->qual, dev->qual, (size_t)C},
-        {host->cigar, dev->cigar, 4 * (size_t)C}, {host->d, dev->d, 2 * (size_t)C}, {host->e, dev->e, 2 * (size_t)C}};
-    for (auto &p : ps)
-        if (p.dst && p.bytes) {
-            hipError_t e = hipMemcpyAsync(p.dst, p.src, p.bytes, hipMemcpyDeviceToHost, s);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
-
 // host-pointer entry point: one staging allocation, H2D, run, D2H
 int dcr_run_batch_host(dcr_ctx *c, const dcr_batch *h, dcr_out *hss, dcr_out *hds) {
     if (!c || !h || !hss || !hds) return fail(DCR_EARG, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t need = plan_io(h, nullptr, nullptr, nullptr);
+    const size_t need = io_bytes(h);
     if (need > c->io.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(c->io.ensure(need));
     }
     dcr_batch db;
     dcr_out dout[2];
-    plan_io(h, (char *)c->io.p, &db, dout);
+    Plan p{(char *)c->io.p};
+    plan_io(h, p, &db, dout);
     HIP_TRY(upload_inputs(h, db, c->stream));
     int rc = dcr_run_batch(c, &db, &dout[0], &dout[1]);
     if (rc) return rc;
@@ -799,8 +819,9 @@ static int host_max_r(const dcr_batch *h) {
     return m;
 }
 
-int dcr_submit(dcr_ctx *c, int slot, const dcr_batch *h, dcr_out *hss, dcr_out *hds, int32_t *read_status) {
-    if (!c || !h || !hss || !hds) return fail(DCR_EARG, "NULL argument");
+// The front of a submit: the copy streams, the slot's events and pinned flag
+// (all created on first use), and the slot must be idle.
+static int slot_open(dcr_ctx *c, int slot, dcr_ctx::Slot **out) {
     if (slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "slot out of range");
     HIP_TRY(hipSetDevice(c->device));
     if (!c->s_h2d) {
@@ -819,21 +840,37 @@ int dcr_submit(dcr_ctx *c, int slot, const dcr_batch *h, dcr_out *hss, dcr_out *
         *S.h_err = 0;
     }
     if (S.busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
-    const size_t need = plan_io(h, nullptr, nullptr, nullptr);
-    if (need > S.buf.cap) HIP_TRY(S.buf.ensure(need + need / 8));   // idle slot: nothing in flight uses it
-    dcr_batch db;
-    dcr_out dout[2];
-    plan_io(h, (char *)S.buf.p, &db, dout);
-    // H2D on the copy stream
-    HIP_TRY(upload_inputs(h, db, c->s_h2d));
+    *out = &S;
+    return DCR_OK;
+}
+
+// After the slot's uploads are enqueued on s_h2d: the consensus kernels on the
+// compute stream once the uploads are done, then the capacity flag.
+static int slot_run(dcr_ctx *c, dcr_ctx::Slot &S, const dcr_batch *h, dcr_batch *db, dcr_out dout[2]) {
     HIP_TRY(hipEventRecord(S.ev_h2d, c->s_h2d));
-    // kernels on the compute stream
     HIP_TRY(hipStreamWaitEvent(c->stream, S.ev_h2d, 0));
     c->max_r_hint = host_max_r(h);
-    int rc = dcr_run_batch(c, &db, &dout[0], &dout[1]);
+    const int rc = dcr_run_batch(c, db, &dout[0], &dout[1]);
     c->max_r_hint = -1;
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(S.h_err, c->w.err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    return DCR_OK;
+}
+
+int dcr_submit(dcr_ctx *c, int slot, const dcr_batch *h, dcr_out *hss, dcr_out *hds, int32_t *read_status) {
+    if (!c || !h || !hss || !hds) return fail(DCR_EARG, "NULL argument");
+    dcr_ctx::Slot *Sp = nullptr;
+    int rc = slot_open(c, slot, &Sp);
+    if (rc) return rc;
+    dcr_ctx::Slot &S = *Sp;
+    const size_t need = io_bytes(h);
+    if (need > S.buf.cap) HIP_TRY(S.buf.ensure(need + need / 8));   // idle slot: nothing in flight uses it
+    dcr_batch db;
+    dcr_out dout[2];
+    Plan p{(char *)S.buf.p};
+    plan_io(h, p, &db, dout);
+    HIP_TRY(upload_inputs(h, db, c->s_h2d));
+    if ((rc = slot_run(c, S, h, &db, dout))) return rc;
     if (read_status && h->n_reads > 0)
         HIP_TRY(hipMemcpy2DAsync(read_status, sizeof(int32_t), (const char *)c->w.info + offsetof(dcr_read_info, status),
                                  sizeof(dcr_read_info), sizeof(int32_t), (size_t)h->n_reads, hipMemcpyDeviceToHost,
@@ -884,68 +921,37 @@ static int64_t stream_bound(const dcr_batch *h, const dcr_wmeta *m) {
 
 int dcr_submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *m, dcr_wres *res) {
     if (!c || !h || !m || !res) return fail(DCR_EARG, "NULL argument");
-    if (slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "slot out of range");
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->s_h2d) {
-        HIP_TRY(hi_prio_stream(&c->s_h2d));
-        HIP_TRY(hi_prio_stream(&c->s_d2h));
-        HIP_TRY(hi_prio_stream(&c->s_fetch));
-    }
-    dcr_ctx::Slot &S = c->slots[slot];
-    if (!S.ev_h2d) {
-        HIP_TRY(hipEventCreateWithFlags(&S.ev_h2d, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&S.ev_comp, hipEventDisableTiming));
-        // the host waits on this one (dcr_wait / dcr_wait_write): blocking, so the
-        // waiting thread sleeps instead of spinning on a core the ingest needs
-        HIP_TRY(hipEventCreateWithFlags(&S.ev_d2h, hipEventDisableTiming | hipEventBlockingSync));
-        HIP_TRY(hipHostMalloc((void **)&S.h_err, sizeof(int), hipHostMallocDefault));
-        *S.h_err = 0;
-    }
-    if (S.busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
+    dcr_ctx::Slot *Sp = nullptr;
+    int rc = slot_open(c, slot, &Sp);
+    if (rc) return rc;
+    dcr_ctx::Slot &S = *Sp;
     const int64_t F = h->n_fam;
     // consensus buffers
-    const size_t need = plan_io(h, nullptr, nullptr, nullptr);
+    const size_t need = io_bytes(h);
     if (need > S.buf.cap) HIP_TRY(S.buf.ensure(need + need / 8));
     dcr_batch db;
     dcr_out dout[2];
-    plan_io(h, (char *)S.buf.p, &db, dout);
+    Plan p{(char *)S.buf.p};
+    plan_io(h, p, &db, dout);
     // writer buffers
     const int64_t B = stream_bound(h, m);
     const int64_t nbm = B / (int64_t)dfl::kMaxIn + 2;
-    const size_t scan1 = dcrw::scan_tmp_bytes((int)(2 * F + 1)), scan2 = dcrw::scan_tmp_bytes((int)(nbm + 1));
-    size_t wo = 0;
-    auto take = [&](size_t bytes) { size_t o = wo; wo = align_up(wo + std::max<size_t>(bytes, 1)); return o; };
-    const size_t o_names = take((size_t)m->n_names + 1);
-    const size_t o_code = take(8 * (size_t)F), o_rx = take(16 * (size_t)F), o_tid = take(4 * (size_t)F);
-    const size_t o_fail = take(4 * (size_t)F), o_dlen = take(8 * (size_t)F);
-    const size_t o_rsz = take(8 * (size_t)(2 * F + 1)), o_roff = take(8 * (size_t)(2 * F + 1));
-    const size_t o_scan = take(std::max(scan1, scan2));
-    const size_t o_stream = take((size_t)B);
-    const size_t o_slots = take((size_t)nbm * dfl::kSlot);
-    // block sizes (+ the scan's total), then k_deflate's block counter
-    const size_t o_bsz = take(8 * (size_t)(nbm + 2)), o_boff = take(8 * (size_t)(nbm + 1));
-    const size_t o_comp = take((size_t)nbm * dfl::kSlot);
-    const size_t o_tot = take(8 * 4);
     const unsigned gd = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nbm, (int64_t)c->n_cu * c->dfl_blocks));
-    const size_t o_tok = take((size_t)gd * dfl::kTokWords * 4);
-    if (wo > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wo + wo / 8));
-    char *wb = (char *)S.wbuf.p;
+    WriterBufs wb;
+    Plan wsz;
+    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb);
+    if (wsz.off > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wsz.off + wsz.off / 8));
+    Plan wp{(char *)S.wbuf.p};
+    plan_writer(F, m->n_names, B, nbm, gd, wp, wb);
     // H2D: inputs and writer metadata on the copy stream
     HIP_TRY(upload_inputs(h, db, c->s_h2d));
-    if (m->n_names) HIP_TRY(hipMemcpyAsync(wb + o_names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
+    if (m->n_names) HIP_TRY(hipMemcpyAsync(wb.names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
     if (F) {
-        HIP_TRY(hipMemcpyAsync(wb + o_code, m->fam_code, 8 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
-        HIP_TRY(hipMemcpyAsync(wb + o_rx, m->fam_rx, 16 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
-        HIP_TRY(hipMemcpyAsync(wb + o_tid, m->fam_tid, 4 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
+        HIP_TRY(hipMemcpyAsync(wb.fam_code, m->fam_code, 8 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
+        HIP_TRY(hipMemcpyAsync(wb.fam_rx, m->fam_rx, 16 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
+        HIP_TRY(hipMemcpyAsync(wb.fam_tid, m->fam_tid, 4 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
     }
-    HIP_TRY(hipEventRecord(S.ev_h2d, c->s_h2d));
-    // consensus kernels on the compute stream
-    HIP_TRY(hipStreamWaitEvent(c->stream, S.ev_h2d, 0));
-    c->max_r_hint = host_max_r(h);
-    int rc = dcr_run_batch(c, &db, &dout[0], &dout[1]);
-    c->max_r_hint = -1;
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(S.h_err, c->w.err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = slot_run(c, S, h, &db, dout))) return rc;
     // record writer
     dcrw::FmtArgs A{};
     A.ss = dout[0];
@@ -955,53 +961,49 @@ int dcr_submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *
     A.ss_col_off = db.ss_col_off;
     A.ds_col_off = db.ds_col_off;
     A.info = c->w.info;
-    A.names = wb + o_names;
-    A.fam_code = (const int64_t *)(wb + o_code);
-    A.fam_rx = (const int64_t *)(wb + o_rx);
-    A.fam_tid = (const int32_t *)(wb + o_tid);
+    A.names = wb.names;
+    A.fam_code = wb.fam_code;
+    A.fam_rx = wb.fam_rx;
+    A.fam_tid = wb.fam_tid;
     A.n_fam = (int32_t)F;
-    A.fam_fail = (int32_t *)(wb + o_fail);
-    A.ds_len_out = (int32_t *)(wb + o_dlen);
-    int64_t *rsz = (int64_t *)(wb + o_rsz);
-    A.rec_size = rsz;
-    A.rec_off = (int64_t *)(wb + o_roff);
-    A.stream = (uint8_t *)(wb + o_stream);
-    HIP_TRY(hipMemsetAsync(rsz, 0, 8 * (size_t)(2 * F + 1), c->stream));
-    HIP_TRY(hipMemsetAsync(wb + o_bsz, 0, 8 * (size_t)(nbm + 2), c->stream));
+    A.fam_fail = wb.fam_fail;
+    A.ds_len_out = wb.ds_len;
+    A.rec_size = wb.rec_size;
+    A.rec_off = wb.rec_off;
+    A.stream = wb.stream;
+    HIP_TRY(hipMemsetAsync(wb.rec_size, 0, 8 * (size_t)(2 * F + 1), c->stream));
+    HIP_TRY(hipMemsetAsync(wb.bsz, 0, 8 * (size_t)(nbm + 2), c->stream));
     if (F) {
         hipLaunchKernelGGL(dcrw::k_famfail, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, c->stream, A);
         const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((2 * F + 3) / 4, (int64_t)c->n_cu * 8));
         hipLaunchKernelGGL(dcrw::k_fmt_size, dim3(g), dim3(256), 0, c->stream, A);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(dcrw::scan_excl_i64(rsz, A.rec_off, (int)(2 * F + 1), (int64_t *)(wb + o_scan), c->stream));
+        HIP_TRY(dcrw::scan_excl_i64(wb.rec_size, wb.rec_off, (int)(2 * F + 1), wb.scan, c->stream));
         hipLaunchKernelGGL(dcrw::k_fmt_write, dim3(g), dim3(256), 0, c->stream, A);
         HIP_TRY(hipGetLastError());
     } else {
-        HIP_TRY(hipMemsetAsync(A.rec_off, 0, 8, c->stream));
+        HIP_TRY(hipMemsetAsync(wb.rec_off, 0, 8, c->stream));
     }
-    int64_t *bsz = (int64_t *)(wb + o_bsz);
-    dcrw::DflArgs D{A.stream, A.rec_off + 2 * F, (uint8_t *)(wb + o_slots), bsz, (uint32_t *)(wb + o_tok), nullptr,
-                    (unsigned long long *)(bsz + nbm + 1)};
+    dcrw::DflArgs D{wb.stream, wb.rec_off + 2 * F, wb.slots, wb.bsz, wb.tok, nullptr,
+                    (unsigned long long *)(wb.bsz + nbm + 1)};
     hipLaunchKernelGGL(dcrw::k_deflate, dim3(gd), dim3(dfl::kT), sizeof(dfl::Shared), c->stream, D);
     HIP_TRY(hipGetLastError());
-    int64_t *boff = (int64_t *)(wb + o_boff);
-    HIP_TRY(dcrw::scan_excl_i64(bsz, boff, (int)(nbm + 1), (int64_t *)(wb + o_scan), c->stream));
-    dcrw::CompactArgs C{(const uint8_t *)(wb + o_slots), bsz, boff, A.rec_off + 2 * F,
-                        (uint8_t *)(wb + o_comp), (int64_t *)(wb + o_tot)};
+    HIP_TRY(dcrw::scan_excl_i64(wb.bsz, wb.boff, (int)(nbm + 1), wb.scan, c->stream));
+    dcrw::CompactArgs C{wb.slots, wb.bsz, wb.boff, wb.rec_off + 2 * F, wb.comp, wb.tot};
     hipLaunchKernelGGL(dcrw::k_compact, dim3(gd), dim3(256), 0, c->stream, C);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(S.ev_comp, c->stream));
     // D2H of the per-family outcome and the totals on the second copy stream
     HIP_TRY(hipStreamWaitEvent(c->s_d2h, S.ev_comp, 0));
     if (F) {
-        HIP_TRY(hipMemcpyAsync(res->fam_fail, A.fam_fail, 4 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
-        HIP_TRY(hipMemcpyAsync(res->ds_len, A.ds_len_out, 8 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
+        HIP_TRY(hipMemcpyAsync(res->fam_fail, wb.fam_fail, 4 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
+        HIP_TRY(hipMemcpyAsync(res->ds_len, wb.ds_len, 8 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
     }
-    HIP_TRY(hipMemcpyAsync(res->totals, wb + o_tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
+    HIP_TRY(hipMemcpyAsync(res->totals, wb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
     HIP_TRY(hipEventRecord(S.ev_d2h, c->s_d2h));
-    S.d_rec_off = A.rec_off;
-    S.d_stream = A.stream;
-    S.d_comp = (uint8_t *)(wb + o_comp);
+    S.d_rec_off = wb.rec_off;
+    S.d_stream = wb.stream;
+    S.d_comp = wb.comp;
     S.n_fam = F;
     S.writer = true;
     S.busy = true;

@@ -37,6 +37,14 @@ struct RecMeta {
 };
 static_assert(sizeof(RecMeta) == 32, "RecMeta is one s_load_dwordx8");
 
+// The per-batch counters, one 64-byte block of the workspace that
+// dcr_run_batch zeroes as a whole; Workspace's err ... lay_next point into it
+// (dcr_debug_counts returns its first ten ints).
+struct Counters {
+    int err, ovf_count[2], fast_count[2], xcount[2], gen_next[2], deep_count, lay_next[2];
+};
+static_assert(sizeof(Counters) <= 64, "the counters are reset with one 64-byte memset");
+
 struct Workspace {
     dcr_read_info *info;    // [n_reads]
     uint32_t *norm_cig;     // [n_cigar] normalised runs (M/I/D)

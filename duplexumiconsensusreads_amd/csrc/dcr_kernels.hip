@@ -1248,13 +1248,12 @@ struct GStamp {
 };
 
 // ------------------------------------------------------------ k_consensus
-// One consensus record (single-strand subfamily or duplex pair) on one wave.
-// FAST: only the staged layout (no insertion column, <= 64 reads, bytes fit the
-// LDS stage, T <= kColsLds); any other record is appended to the overflow list
-// and processed by the general kernel.
-template <bool DUPLEX, bool FAST>
+// One consensus record (single-strand subfamily or duplex pair) of the general
+// list on one wave (k_consensus_general): every layout, the staged one
+// included.
+template <bool DUPLEX>
 __device__ __forceinline__ void process_record(const Args &a, const int64_t rec, WaveLds &W, const double2 *s_lut,
-                                               const double *s_qthr, const uint32_t *s_wtab, const bool dec,
+                                               const double *s_qthr, const uint32_t *s_wtab, const bool decided,
                                                const int lane, GStamp &gs) {
     const dcr_params *P = a.P;
     gs.start();
@@ -1379,20 +1378,10 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
     if (DCR_ABL == 10 && ins && !big) return;     // diagnostic: ... without the <= 64-read insertion layout
     if (DCR_ABL == 11 && !ins) return;            // diagnostic: ... without the records free of insertions
     if (DCR_ABL == 12 && ins) return;             // diagnostic: ... without any insertion layout
-    if constexpr (FAST) {
-        if (!staged || !cols_lds) {          // general kernel takes it
-            if (lane == 0) {
-                const int idx = atomicAdd(&a.ws.ovf_count[DUPLEX ? 1 : 0], 1);
-                a.ws.ovf[idx] = (int)rec;
-            }
-            return;
-        }
-    }
 
-    // ---- k_decide proved every column's call from integer LLR bounds: the
-    // tiles below take call / d / e from its column words instead of forming
-    // the products
-    const bool decided = !FAST && dec;
+    // ---- decided: k_decide proved every column's call from integer LLR
+    // bounds; the tiles below take call / d / e from its column words instead
+    // of forming the products
 
     // ---- phase 0: element codes into LDS (every record whose bytes fit: the
     // fast layout reads them by column, the insertion layout by read)
@@ -1433,7 +1422,7 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
     // insertion records that k_ins_layout laid out: the tiles load their rows
     // (no column steps, flag pass or windows here)
     const int64_t lrec = (DUPLEX ? 4 * (int64_t)a.in.n_fam : 0) + rec;
-    const bool laid = !FAST && ins && cols_lds && R <= kBigCh * kWave && a.ws.lay_base[lrec] > 0;
+    const bool laid = ins && cols_lds && R <= kBigCh * kWave && a.ws.lay_base[lrec] > 0;
     uint64_t imask[4] = {0ull, 0ull, 0ull, 0ull};
     const uint16_t *lrows = nullptr;
     if (laid) {
@@ -1442,7 +1431,7 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
         for (int w = 0; w < 4; ++w) imask[w] = mk[w];
         lrows = a.ws.lay + (DUPLEX ? (int64_t)a.in.n_reads + 2 * rec : (int64_t)a.in.sub_off[rec]) * kLayRow;
     }
-    const bool regbig = !FAST && ins && big && !DUPLEX && R <= kBigCh * kWave && !laid;
+    const bool regbig = ins && big && !DUPLEX && R <= kBigCh * kWave && !laid;
     struct SlimRead {
         int pos, len, ncig;
         const uint32_t *cig;
@@ -1490,7 +1479,7 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
         }
         wave_fence();
     }
-    if (!FAST && ins && big && !DUPLEX && !regbig && !laid) {
+    if (ins && big && !DUPLEX && !regbig && !laid) {
         for (int c = 0; c < R; c += kWave) {
             const int r = c + lane;
             if (r < R) {
@@ -1614,8 +1603,6 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
             };
             accumulate(A, R, src, s_lut);
             gs.mark(4);
-        } else if (FAST) {
-            // unreachable: the fast kernel only keeps staged records
         } else if (!ins) {
             auto src = [&](int r) -> uint32_t {
                 const ReadRef rd = get_read<DUPLEX>(a, rec, r);
@@ -1634,8 +1621,6 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
             // second), every load of a chunk issued before its tile is used
             const uint64_t mw = c0 < 64 ? imask[0] : c0 < 128 ? imask[1] : c0 < 192 ? imask[2] : imask[3];
             ins_col = live && ((mw >> (t & 63)) & 1ull) != 0;
-            const int tt = lane & (kTileIns - 1);
-            const int hcol = c0 + tt, hi = lane >> 5;
             for (int cb = 0; cb < R; cb += kWave) {
                 const int nr = min(kWave, R - cb);
                 // this tile of the chunk's reads: nr rows of 64 bytes, one block
@@ -1648,8 +1633,6 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
                     if (u * kWave + lane < 4 * nr) dst4[u * kWave + lane] = q[u];
-                (void)hi;
-                (void)hcol;
                 sfence();
                 gs.mark(3);
                 auto src = [&](int rr) -> uint32_t { return live ? (uint32_t)W.tile[rr][lane & (kTileIns - 1)] : kPad; };
@@ -1940,7 +1923,7 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
         n2 -= n2 % 8;
         const double left = leaf(0, n2);
         total = left + leaf(n2, n_de - n2);
-    } else if (!FAST) {
+    } else {
         // general depth: explicit uniform stack in LDS
         int *stk_off = W.stk_off, *stk_n = W.stk_n, *stk_stage = W.stk_stage;
         double *stk_left = W.stk_left;
@@ -1977,8 +1960,6 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
             }
         }
         total = ret;
-    } else {
-        total = 0.0;   // unreachable in the fast kernel (T <= kColsLds)
     }
     total = 0.0 + total;
     const double mean = total / (double)n_de;
@@ -2255,18 +2236,6 @@ __device__ __forceinline__ int opaque(int v) {
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-
-// IEEE max / min of two doubles known not to be NaN (no canonicalising moves)
-__device__ __forceinline__ double vmax_f64(double x, double y) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-}
-__device__ __forceinline__ double vmin_f64(double x, double y) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-}
 
 
 // inclusive prefix max over the wave (DPP row shifts, then row broadcasts)
@@ -4062,7 +4031,7 @@ __global__ __launch_bounds__(kBlock, DCR_GEN_OCC) void k_consensus_general(Args 
     for (int i = blockIdx.x * kWavesPerBlock + wave;;) {
         if (i >= n) break;
         const int v = a.ws.ovf[i];                  // bit 31: k_decide decided every column
-        process_record<DUPLEX, false>(a, v & 0x7fffffff, s_wave[wave], s_lut, s_qthr, s_wtab, v < 0, lane, gs);
+        process_record<DUPLEX>(a, v & 0x7fffffff, s_wave[wave], s_lut, s_qthr, s_wtab, v < 0, lane, gs);
         if (nw >= n) break;
         // one claim per wave, by its first active lane (any lane may carry it)
         const uint64_t act = __ballot(1);
