@@ -4,9 +4,11 @@
 // (CPython's MT19937, bit for bit), and packing of processed families into
 // the dcr_batch layout the GPU consumes.
 //
-// Per batch the work splits into a serial walk (record boundaries, filters,
-// grouping, RNG; a few loads per record) and parallel parts (inflate of the
-// next window of BGZF blocks; family checks and per-read copies of sequence /
+// Per batch the work splits into a serial walk (capacities, reservation,
+// counters, RNG: per family where the scanner's run table has the family
+// whole, else per record: filters, grouping) and parallel parts (inflate of the
+// next window of BGZF blocks; record parse, family boundaries and family
+// sums; family checks and per-read copies of sequence /
 // qualities / CIGAR into the caller's pinned arrays, queued by the walk as
 // family tasks).
 //
@@ -391,6 +393,85 @@ struct RecParser {
 
 };
 
+// What the batch layout needs to know of a list of reads: the whole
+// list's totals, and per subfamily (split_family :132-154, from parse_at)
+// the reads, bases, CIGAR ops, column bounds, '=' / 'X' reads and first read.
+struct FamSum {
+    int64_t n = 0, nb = 0, nc = 0, bytes = 0;
+    int64_t cnt[4] = {0, 0, 0, 0}, nbk[4] = {0, 0, 0, 0}, nck[4] = {0, 0, 0, 0};
+    int64_t mn[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0};   // min pos, max end_kept
+    int16_t eqx[4] = {0, 0, 0, 0};
+    const Rec *first[4] = {nullptr, nullptr, nullptr, nullptr};
+
+    void add(const Rec *r) {
+        ++n;
+        nb += r->l_seq;
+        nc += r->n_cig;
+        bytes += r->len;
+        const int k = r->subk;
+        if (k < 0) return;
+        if (!first[k]) {
+            first[k] = r;
+            mn[k] = r->pos;
+            mx[k] = r->end_kept;
+        } else {
+            if (r->pos < mn[k]) mn[k] = r->pos;
+            if (r->end_kept > mx[k]) mx[k] = r->end_kept;
+        }
+        ++cnt[k];
+        nbk[k] += r->l_seq;
+        nck[k] += r->n_cig;
+        if (eqx[k] < 0x7fff && r->eqx) ++eqx[k];
+    }
+    // the reads of `b` follow this list's
+    void append(const FamSum &b) {
+        n += b.n;
+        nb += b.nb;
+        nc += b.nc;
+        bytes += b.bytes;
+        for (int k = 0; k < 4; ++k) {
+            if (!b.first[k]) continue;
+            if (!first[k]) {
+                first[k] = b.first[k];
+                mn[k] = b.mn[k];
+                mx[k] = b.mx[k];
+            } else {
+                mn[k] = std::min(mn[k], b.mn[k]);
+                mx[k] = std::max(mx[k], b.mx[k]);
+            }
+            cnt[k] += b.cnt[k];
+            nbk[k] += b.nbk[k];
+            nck[k] += b.nck[k];
+            eqx[k] = (int16_t)std::min(0x7fff, (int)eqx[k] + (int)b.eqx[k]);
+        }
+    }
+};
+
+// do a and b, records of window wb, carry the same MI prefix?
+inline bool same_code(const uint8_t *wb, const Rec &a, const Rec &b) {
+    if (a.l_code != b.l_code) return false;
+    if (a.l_code <= sizeof a.code) {            // zero-padded inline copies: three words
+        uint64_t x[3], y[3];
+        std::memcpy(x, a.code, sizeof x);
+        std::memcpy(y, b.code, sizeof y);
+        return ((x[0] ^ y[0]) | (x[1] ^ y[1]) | (x[2] ^ y[2])) == 0;
+    }
+    return std::memcmp(wb + a.off + a.o_mi, wb + b.off + b.o_mi, a.l_code) == 0;
+}
+
+// A run of the record index: a maximal range of consecutive entries that
+// are all plain (parsed, passing, MI a string) and carry the same MI
+// prefix, with the summary of its records; a record that is not plain is a
+// run of its own, marked slow.  The walk takes a run that is a whole family
+// in one step.
+struct Run {
+    uint32_t first = 0, n = 0;      // index entries [first, first + n)
+    bool slow = false;
+    bool cont = false;              // run stage only: goes on from the item before
+    FamSum sum;                     // sum.first[] point into the chunk's recs
+};
+inline bool plain(const Rec &r) { return r.perr == 0 && r.pf == 1 && r.mi_type == 'Z'; }
+
 // Background BGZF inflate and record index, two pipeline stages ahead of the
 // record walk:
 //   inflate thread  reads the file and inflates ~32 MiB runs of whole blocks
@@ -398,7 +479,9 @@ struct RecParser {
 //   scanner thread  follows the block_size chain through the chunk (the BAM
 //                   header first) and parses every record that starts and
 //                   ends inside it (on a second pool), so the walk gets
-//                   parsed records and does no pointer chasing of its own.
+//                   parsed records and does no pointer chasing of its own;
+//                   the same pool cuts the index into runs (Run) and sums
+//                   each, so the walk takes a whole family in one step.
 // Each chunk keeps headroom in front of its data so the walk can put the
 // bytes it still needs (the open family, a record straddling the chunk
 // boundary) right before the new data without moving it: record offsets are
@@ -416,34 +499,46 @@ struct Chunk {
     std::vector<Rec> recs;          // boundary in this chunk and ending in it (off from buf start)
     std::vector<size_t> offs;       // the chain's record starts (parse stage input)
     bool chained = false;           // the chain walked this chunk (its offs are valid)
+    std::vector<Run> runs;          // the runs of recs in order, when indexed (the run stage)
+    std::vector<std::vector<Run>> item_runs;   // run stage scratch: the runs found inside each item
+    std::vector<size_t> item_at;               // and where each item's runs go in `runs`
 };
 
-// Record-index vectors of released chunks, kept for the next ingest of the
-// process (as HugeCache keeps the chunk buffers): freeing four ~13 MB vectors
-// per ingest unmapped their pages inside every CLI pass (~18 ms of a close)
+// Record-index vectors of released chunks (the records and their run table),
+// kept for the next ingest of the process (as HugeCache keeps the chunk
+// buffers): freeing four ~13 MB vectors per ingest unmapped their pages
+// inside every CLI pass (~18 ms of a close)
 class RecsCache {
   public:
     static RecsCache &get() {
         static RecsCache c;
         return c;
     }
-    std::vector<Rec> take() {
+    void take(Chunk &c) {
         std::lock_guard<std::mutex> g(mu_);
-        if (spare_.empty()) return {};
-        std::vector<Rec> v = std::move(spare_.back());
+        if (spare_.empty()) return;
+        Spare &s = spare_.back();
+        c.recs = std::move(s.recs);
+        c.runs = std::move(s.runs);
+        c.item_runs = std::move(s.item_runs);
         spare_.pop_back();
-        return v;
     }
-    void give(std::vector<Rec> &&v) {
+    void give(Chunk &c) {
         std::lock_guard<std::mutex> g(mu_);
-        if (spare_.size() >= 16 || v.capacity() == 0) return;
-        v.clear();                          // keeps the capacity
-        spare_.push_back(std::move(v));
+        if (spare_.size() >= 16 || c.recs.capacity() == 0) return;
+        c.recs.clear();                     // keeps the capacity
+        c.runs.clear();
+        spare_.push_back(Spare{std::move(c.recs), std::move(c.runs), std::move(c.item_runs)});
     }
 
   private:
+    struct Spare {
+        std::vector<Rec> recs;
+        std::vector<Run> runs;
+        std::vector<std::vector<Run>> item_runs;
+    };
     std::mutex mu_;
-    std::vector<std::vector<Rec>> spare_;
+    std::vector<Spare> spare_;
 };
 
 // Thread pools of closed ingests, kept for the next ones of the process: a
@@ -512,7 +607,7 @@ class Inflater {
           spool_(PoolCache::get().take(env_threads("DCR_SCAN_THREADS", std::max(1, n_threads / 2)))), rp_(rp),
           end_coff_(end_coff),
           end_uoff_(end_uoff) {
-        for (auto &c : chunks_) c.recs = RecsCache::get().take();
+        for (auto &c : chunks_) RecsCache::get().take(c);
         if (ranged) {
             st_ = kRec;
             skip_ = start_uoff;
@@ -596,7 +691,7 @@ class Inflater {
                 if (c.pin) hook_.host_free(hook_.user, c.pin);
             if (stage_pin_) hook_.host_free(hook_.user, stage_pin_);
         }
-        for (auto &c : chunks_) RecsCache::get().give(std::move(c.recs));
+        for (auto &c : chunks_) RecsCache::get().give(c);
         PoolCache::get().give(std::move(pool_));
         PoolCache::get().give(std::move(spool_));
     }
@@ -690,7 +785,7 @@ class Inflater {
         }
         cv_.notify_all();
     }
-    double scan_s = 0, index_parse_s = 0;   // DCR_INGEST_PROF
+    double scan_s = 0, index_parse_s = 0, runs_s = 0;   // DCR_INGEST_PROF
 
   private:
     void loop() {
@@ -760,6 +855,7 @@ class Inflater {
     // previous chunk (a field or a skip may straddle the boundary)
     void chain(Chunk &c) {
         c.recs.clear();
+        c.runs.clear();
         c.indexed = false;
         c.chained = false;
         std::vector<size_t> &offs_ = c.offs;
@@ -836,21 +932,75 @@ class Inflater {
         c.chained = true;
         if (prof_) scan_s += now() - t0;
     }
+    // The records' fields and the run table of the index, on the pool in
+    // items of 512 records.  An item parses its records and, while they are
+    // hot in its core's cache, finds the runs inside it and sums their
+    // records (record i against record i - 1).  After the barrier the
+    // item's first record is compared with the last of the item before
+    // (complete now), each item puts its runs at their place in c.runs, and
+    // the owner of a run that goes on into later items adds their leading
+    // partial sums.  The work that is not on the pool is per item.
     void parse(Chunk &c) {
         if (!c.chained) return;
         const double t1 = prof_ ? now() : 0;
         const std::vector<size_t> &offs_ = c.offs;
         c.recs.resize(offs_.size());
+        const std::vector<Rec> &R = c.recs;
         const uint8_t *base = c.data();
         const size_t chunk = 512;
-        spool_->run((offs_.size() + chunk - 1) / chunk, [&](size_t k) {
-            const size_t e = std::min(offs_.size(), (k + 1) * chunk);
-            for (size_t i = k * chunk; i < e; ++i)
+        const size_t items = (offs_.size() + chunk - 1) / chunk;
+        if (c.item_runs.size() < items) c.item_runs.resize(items);
+        spool_->run(items, [&](size_t k) {
+            const size_t b = k * chunk, e = std::min(offs_.size(), (k + 1) * chunk);
+            for (size_t i = b; i < e; ++i)
                 c.recs[i].perr = (uint8_t)rp_.parse_at(base, kHead + offs_[i], c.recs[i]);
+            std::vector<Run> &L = c.item_runs[k];
+            L.clear();
+            for (size_t i = b; i < e; ++i) {
+                const Rec &r = R[i];
+                const bool pl = plain(r);
+                if (i == b || !pl || !plain(R[i - 1]) || !same_code(base, r, R[i - 1])) {
+                    L.emplace_back();
+                    L.back().first = (uint32_t)i;
+                    L.back().slow = !pl;
+                }
+                ++L.back().n;
+                L.back().sum.add(&r);
+            }
+            return true;
+        });
+        const double t2 = prof_ ? now() : 0;
+        c.item_at.resize(items + 1);
+        size_t total = 0;
+        for (size_t k = 0; k < items; ++k) {
+            std::vector<Run> &L = c.item_runs[k];
+            const size_t b = k * chunk;
+            L[0].cont = k > 0 && !L[0].slow && plain(R[b - 1]) && same_code(base, R[b], R[b - 1]);
+            c.item_at[k] = total;
+            total += L.size() - (L[0].cont ? 1 : 0);
+        }
+        c.item_at[items] = total;
+        c.runs.resize(total);
+        spool_->run(items, [&](size_t k) {
+            const std::vector<Run> &L = c.item_runs[k];
+            size_t at = c.item_at[k];
+            for (size_t j = L[0].cont ? 1 : 0; j < L.size(); ++j) {
+                Run &u = c.runs[at++];
+                u = L[j];
+                if (j + 1 < L.size()) continue;
+                for (size_t m = k + 1; m < items && c.item_runs[m][0].cont; ++m) {
+                    u.n += c.item_runs[m][0].n;
+                    u.sum.append(c.item_runs[m][0].sum);
+                    if (c.item_runs[m].size() > 1) break;
+                }
+            }
             return true;
         });
         c.indexed = true;
-        if (prof_) index_parse_s += now() - t1;
+        if (prof_) {
+            index_parse_s += t2 - t1;
+            runs_s += now() - t2;
+        }
     }
     static double now() {
         return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -1061,7 +1211,9 @@ class Inflater {
 struct IngestProf {
     bool on = std::getenv("DCR_INGEST_PROF") != nullptr;
     double wait_chunk = 0, scan = 0, parse = 0, walk_total = 0, complete = 0, tasks_wait = 0;
+    double walk_in = 0, prefetch = 0;    // inside walk(), and of that inside prefetch_records()
     int64_t indexed = 0;
+    int64_t fams = 0, run_fams = 0;      // families queued, and those taken as a run of the scanner's table
     static double now() {
         return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     }
@@ -1109,11 +1261,12 @@ struct dcr_ingest {
         if (prof.on)
             std::fprintf(stderr,
                          "[ingest] walk %.3f s: chunk wait %.3f, serial scan %.3f, parse %.3f, "
-                         "families %.3f, family tasks wait %.3f; scanner stage: chain %.3f, parse %.3f; indexed "
-                         "records %lld of %lld\n",
+                         "families %.3f, family tasks wait %.3f, record loop %.3f; scanner stage: chain %.3f, "
+                         "parse %.3f, runs %.3f; indexed records %lld of %lld; run path %lld of %lld families\n",
                          prof.walk_total, prof.wait_chunk, prof.scan, prof.parse, prof.complete, prof.tasks_wait,
-                         infl ? infl->scan_s : 0.0,
-                         infl ? infl->index_parse_s : 0.0, (long long)prof.indexed, (long long)records);
+                         prof.walk_in - prof.prefetch - prof.complete, infl ? infl->scan_s : 0.0,
+                         infl ? infl->index_parse_s : 0.0, infl ? infl->runs_s : 0.0, (long long)prof.indexed,
+                         (long long)records, (long long)prof.run_fams, (long long)prof.fams);
         infl.reset();             // stops the inflate thread before the file closes
         if (f) std::fclose(f);
         PoolCache::get().give(std::move(pool));
@@ -1385,43 +1538,13 @@ struct dcr_ingest {
         return rc;
     }
 
-    // What the batch layout needs to know of a list of reads: the whole
-    // list's totals, and per subfamily (split_family :132-154, from parse_at)
-    // the reads, bases, CIGAR ops, column bounds, '=' / 'X' reads and first read.
-    struct FamSum {
-        int64_t n = 0, nb = 0, nc = 0, bytes = 0;
-        int64_t cnt[4] = {0, 0, 0, 0}, nbk[4] = {0, 0, 0, 0}, nck[4] = {0, 0, 0, 0};
-        int64_t mn[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0};   // min pos, max end_kept
-        int16_t eqx[4] = {0, 0, 0, 0};
-        const Rec *first[4] = {nullptr, nullptr, nullptr, nullptr};
-    };
     static FamSum summarize(const Rec *const *rs, size_t n) {
         FamSum S;
-        S.n = (int64_t)n;
-        for (size_t i = 0; i < n; ++i) {
-            const Rec *r = rs[i];
-            S.nb += r->l_seq;
-            S.nc += r->n_cig;
-            S.bytes += r->len;
-            const int k = r->subk;
-            if (k < 0) continue;
-            if (!S.first[k]) {
-                S.first[k] = r;
-                S.mn[k] = r->pos;
-                S.mx[k] = r->end_kept;
-            } else {
-                if (r->pos < S.mn[k]) S.mn[k] = r->pos;
-                if (r->end_kept > S.mx[k]) S.mx[k] = r->end_kept;
-            }
-            ++S.cnt[k];
-            S.nbk[k] += r->l_seq;
-            S.nck[k] += r->n_cig;
-            if (S.eqx[k] < 0x7fff && r->eqx) ++S.eqx[k];
-        }
+        for (size_t i = 0; i < n; ++i) S.add(rs[i]);
         return S;
     }
 
-    // Is there room in the batch for the open family, all its reads counted
+    // Is there room in the batch for the family of first record r0, all its reads counted
     // (the bound also of a family that samples, tested before any draw)?
     // Names: reserve_family writes the code and two RX strings, those of the
     // first A1 and B1 read of the list it is given.  For a family checked
@@ -1431,9 +1554,8 @@ struct dcr_ingest {
     // yet drawn here, but reserved only after check_family: every RX is then
     // the first record's or its swapped halves, no longer than it.  Twice the
     // longest of the three covers both.
-    bool family_fits(const FamSum &S) const {
+    bool family_fits(const FamSum &S, const Rec &r0) const {
         const dcr_host_batch *b = hb;
-        const Rec &r0 = *fam.front();
         int64_t l_rx = r0.l_rx;
         for (int k = 0; k < 4; k += 2)
             if (S.first[k]) l_rx = std::max<int64_t>(l_rx, S.first[k]->l_rx);
@@ -1443,15 +1565,14 @@ struct dcr_ingest {
                b->n_names + names_need <= b->cap_names && b->n_side_filt + S.bytes <= b->cap_side;
     }
 
-    // The open family's place in the batch, from the summary of the reads it
+    // The place in the batch of the family of first record r0, from the summary of the reads it
     // packs (all of them, or the sample): table entry, names and counters;
     // filtered (!enough), filt_bytes of side_filt; else the processed family's
     // entries and its read / base / CIGAR / column ranges.  Returns the task
     // with the offsets and the state before the family; its records, window
     // and `checked` are the caller's to set.
-    FamTask reserve_family(const FamSum &S, int sampled, bool enough, int64_t filt_bytes) {
+    FamTask reserve_family(const FamSum &S, const Rec &r0, int sampled, bool enough, int64_t filt_bytes) {
         dcr_host_batch *b = hb;
-        const Rec &r0 = *fam.front();
         FamTask T;
         T.fam_before = b->n_fam;
         T.names_before = b->n_names;
@@ -1522,13 +1643,13 @@ struct dcr_ingest {
         return T;
     }
 
-    // check_number_reads' draws (:157-188) for the open family, whose
+    // check_number_reads' draws (:157-188) for the family fr[0, n), whose
     // subfamilies `sampled` names exceed max_reads: random.sample per
     // subfamily in order, then `pick` holds the family's reads to pack, in
     // split order, a sampled subfamily's in selection order.  1 done, -1 the
     // state gate gave no state.
     std::vector<const Rec *> split, pick;
-    int sample_family(const FamSum &S, int sampled) {
+    int sample_family(RecList fr, size_t n, const FamSum &S, int sampled) {
         if (gate_fn && !gate_open) {
             gate_open = true;
             if (gate_fn(gate_user, rng.mt, &rng.index) != 0 || rng.index < 0 || rng.index > 624) {
@@ -1543,8 +1664,8 @@ struct dcr_ingest {
             n_split += (size_t)S.cnt[k];
         }
         split.resize(n_split);
-        for (const Rec *r : fam)
-            if (r->subk >= 0) split[fill[r->subk]++] = r;
+        for (size_t i = 0; i < n; ++i)
+            if (fr[i]->subk >= 0) split[fill[fr[i]->subk]++] = fr[i];
         pick.clear();
         for (int k = 0; k < 4; ++k) {
             const Rec *const *sk = split.data() + at[k];
@@ -1560,51 +1681,62 @@ struct dcr_ingest {
         return 1;
     }
 
-    // preprocess_family up to the read loop (:1248-1264) for the open family:
-    // reserve it in the batch and queue its checks and copies.  A family that
-    // samples comes after every queued check and is checked and sampled
-    // here, in input order.  Returns 1 done, 0 no room in this batch (nothing
-    // changed, no draw made), -1 the reference stops here (batch error set)
-    // or the ingest fails.
-    int queue_family() {
-        dcr_host_batch *b = hb;
-        FamSum S = summarize(fam.data(), fam.size());
-        const int64_t filt_bytes = S.bytes;
-        int sampled = 0;
-        bool enough = true;
-        for (int k = 0; k < 4; ++k) {                      // check_number_reads (:157-188)
-            if (S.cnt[k] < cfg.min_reads) { enough = false; break; }
+    // check_number_reads' counts (:157-188): does every subfamily have
+    // min_reads, and which of them (bits of `sampled`) exceed max_reads
+    bool count_reads(const FamSum &S, int &sampled) const {
+        sampled = 0;
+        for (int k = 0; k < 4; ++k) {
+            if (S.cnt[k] < cfg.min_reads) return false;
             if (S.cnt[k] > cfg.max_reads) sampled |= 1 << k;
         }
-        // the family's records consecutive in the record index (not copies in fam_store)?
-        bool contig = !sampled && (fam.front() < fam_store.data() || fam.front() >= fam_store.data() + fam_store.size());
-        for (size_t j = 1; j < fam.size() && contig; ++j) contig = fam[j] == fam.front() + j;
-        if (((sampled && tk_unchecked) || (!contig && pend_recs.size() + fam.size() > pend_recs.capacity()) ||
+        return true;
+    }
+
+    // preprocess_family up to the read loop (:1248-1264) for a complete
+    // family of summary S: its n records are the list rs, or (rs null) the
+    // consecutive records cbase[0, n) of the record index; both given, the
+    // list's records are those (a family that samples always comes as a
+    // list).  Reserves it in the batch and queues its checks and copies.  A
+    // family that samples comes after every queued check and is checked and
+    // sampled here, in input order.  `consume`: records of the family the
+    // walk has not counted yet (the run path), counted once the family has
+    // its room.  Returns 1 done, 0 no room in this batch (nothing changed,
+    // no draw made), -1 the reference stops here (batch error set) or the
+    // ingest fails.
+    int queue_family(const Rec *const *rs, const Rec *cbase, size_t n, FamSum S, size_t consume) {
+        dcr_host_batch *b = hb;
+        const RecList fr{rs, cbase};
+        const Rec &r0 = *fr[0];
+        const int64_t filt_bytes = S.bytes;
+        int sampled = 0;
+        const bool enough = count_reads(S, sampled);
+        const bool contig = cbase != nullptr && !sampled;
+        if (((sampled && tk_unchecked) || (!contig && pend_recs.size() + n > pend_recs.capacity()) ||
              tasks.size() == tasks.capacity()) &&
             flush_tasks() < 0)
             return -1;
-        if (!family_fits(S)) {
+        if (!family_fits(S, r0)) {
             if (b->n_tab == 0 && b->n_side_exc == 0) {
                 if (flush_tasks() < 0) return -1;
                 return fail_capacity("one family exceeds the batch capacities");
             }
             return 0;
         }
-        const Rec *const *recs = fam.data();
-        size_t n = fam.size();
+        passed += (int64_t)consume;
+        records += (int64_t)consume;
         if (sampled) {
             std::string msg;
-            const int kind = check_family(RecList{fam.data(), nullptr}, fam.size(), wb, umi2_, msg);
+            const int kind = check_family(fr, n, wb, umi2_, msg);
             if (kind != DCR_ERR_NONE) return stop(kind, msg);
             if (cfg.max_reads < 0) return stop(DCR_ERR_VALUE, "Sample larger than population or is negative");
-            if (sample_family(S, sampled) < 0) return -1;
+            if (sample_family(fr, n, S, sampled) < 0) return -1;
             if (enough) {
                 S = summarize(pick.data(), pick.size());
-                recs = pick.data();
+                rs = pick.data();
                 n = pick.size();
             }
         }
-        FamTask T = reserve_family(S, sampled, enough, filt_bytes);
+        FamTask T = reserve_family(S, r0, sampled, enough, filt_bytes);
         T.w = wb;
         T.checked = sampled != 0;
         T.rb = (uint32_t)pend_recs.size();
@@ -1616,10 +1748,10 @@ struct dcr_ingest {
         // the next window (need() rewrites their offsets): the task keeps copies
         const Rec *fs0 = fam_store.data(), *fs1 = fs0 + fam_store.size();
         if (contig) {
-            T.cbase = fam.front();
+            T.cbase = cbase;
         } else {
             for (size_t j = 0; j < n; ++j) {
-                const Rec *r = recs[j];
+                const Rec *r = rs[j];
                 if (r >= fs0 && r < fs1) {
                     task_recs.push_back(*r);
                     pend_recs.push_back(&task_recs.back());
@@ -1631,8 +1763,17 @@ struct dcr_ingest {
         tk_reads += n;
         tk_unchecked += !sampled;
         tasks.push_back(std::move(T));
+        ++prof.fams;
         if (tk_reads >= kTkReads) release_retired();
         return 1;
+    }
+    // the open family, complete: its summary, and whether its records are
+    // consecutive in the record index (not copies in fam_store)
+    int queue_open_family() {
+        const FamSum S = summarize(fam.data(), fam.size());
+        bool contig = fam.front() < fam_store.data() || fam.front() >= fam_store.data() + fam_store.size();
+        for (size_t j = 1; j < fam.size() && contig; ++j) contig = fam[j] == fam.front() + j;
+        return queue_family(fam.data(), contig ? fam.front() : nullptr, fam.size(), S, 0);
     }
 
     // parsed records ahead of the walk: rqp[rq_pos, rq_n) (the scanner's
@@ -1641,6 +1782,8 @@ struct dcr_ingest {
     std::vector<Rec> rq;
     std::vector<size_t> rq_off;
     size_t rq_pos = 0, rq_n = 0;
+    bool rq_indexed = false;             // rqp points into cur->recs
+    size_t run_i = 0;                    // then: no run of cur->runs before this one starts at or after rqp[rq_pos]
 
     // scan the next complete records of the window (block_size chain) and
     // parse them on the pool; 1 some, 0 end of data, -1 error (g_err)
@@ -1663,6 +1806,7 @@ struct dcr_ingest {
         materialize_family();
         if (rq.size() < kRQ) { rq.resize(kRQ); rq_off.resize(kRQ); }
         rq_pos = rq_n = 0;
+        rq_indexed = false;
         size_t n = 0;
         double ts = prof.on ? IngestProf::now() : 0;
         size_t stop_at = SIZE_MAX;
@@ -1675,6 +1819,8 @@ struct dcr_ingest {
                     rqp = R.data() + ci;
                     rq_n = R.size() - ci;
                     ci = R.size();
+                    rq_indexed = true;
+                    run_i = 0;
                     prof.indexed += (int64_t)rq_n;
                     return 1;
                 }
@@ -1733,16 +1879,6 @@ struct dcr_ingest {
         return r.l_code <= sizeof r.code ? r.code : (const char *)at(r, r.o_mi);
     }
     const char *rx_of(const Rec &r) const { return (const char *)at(r, r.o_rx); }
-    bool same_code(const Rec &a, const Rec &b) const {
-        if (a.l_code != b.l_code) return false;
-        if (a.l_code <= sizeof a.code) {            // zero-padded inline copies: three words
-            uint64_t x[3], y[3];
-            std::memcpy(x, a.code, sizeof x);
-            std::memcpy(y, b.code, sizeof y);
-            return ((x[0] ^ y[0]) | (x[1] ^ y[1]) | (x[2] ^ y[2])) == 0;
-        }
-        return std::memcmp(code_of(a), code_of(b), a.l_code) == 0;
-    }
 
     // check_family_UMIs (:100-113), every RX is umi1 or its swapped halves,
     // then check_family_rnames (:116-128), over the family's records fr[0, n)
@@ -1831,6 +1967,7 @@ struct dcr_ingest {
         }
         const double tw = prof.on ? IngestProf::now() : 0;
         int rc = walk();
+        if (prof.on) prof.walk_in += IngestProf::now() - tw;
         if (flush_tasks() < 0 && rc >= 0) rc = -1;
         if (prof.on) prof.walk_total += IngestProf::now() - tw;
         hb = nullptr;
@@ -1845,19 +1982,55 @@ struct dcr_ingest {
         dcr_host_batch *b = hb;
         for (;;) {
             if (rq_pos == rq_n) {
+                const double tp = prof.on ? IngestProf::now() : 0;
                 const int st = prefetch_records();
+                if (prof.on) prof.prefetch += IngestProf::now() - tp;
                 if (st < 0) return -1;
                 if (st == 0) {
                     // end of input: the last family (:1610-1631)
                     if (!started && !mid_end) return stop(DCR_ERR_TYPE, "'NoneType' object is not subscriptable");
                     if (!fam.empty()) {
-                        const int c = queue_family();
+                        const int c = queue_open_family();
                         if (c <= 0) return c;
                         fam.clear();
                     }
                     finished = true;
                     b->end_kind = DCR_END_EOF;
                     return 1;
+                }
+            }
+            // No family open and a run of the scanner's table starts here
+            // that is a whole family -- plain records, and so is the next
+            // run's first: one with another MI prefix, which is what closes
+            // a family below (a slow record may be an excluded read inside
+            // the family; the index's last run may go on in the next chunk):
+            // the family in one step, from the run's summary.
+            if (rq_indexed && fam.empty()) {
+                const std::vector<Run> &RT = cur->runs;
+                const size_t a = (size_t)(rqp - cur->recs.data()) + rq_pos;
+                while (run_i < RT.size() && RT[run_i].first < a) ++run_i;
+                if (run_i + 1 < RT.size() && RT[run_i].first == a && !RT[run_i].slow && !RT[run_i + 1].slow &&
+                    rqp[rq_pos].off == wpos) {
+                    const Run &u = RT[run_i];
+                    const Rec *r0 = rqp + rq_pos;
+                    const double tc = prof.on ? IngestProf::now() : 0;
+                    int sampled = 0;
+                    count_reads(u.sum, sampled);
+                    if (sampled) {
+                        fam.resize(u.n);
+                        for (uint32_t j = 0; j < u.n; ++j) fam[j] = r0 + j;
+                    }
+                    const int c = queue_family(sampled ? fam.data() : nullptr, r0, u.n, u.sum, u.n);
+                    fam.clear();
+                    if (prof.on) prof.complete += IngestProf::now() - tc;
+                    if (c <= 0) return c;      // 0: batch full, nothing consumed: the next batch starts at this run
+                    started = true;
+                    wpos = r0[u.n - 1].off + r0[u.n - 1].len;
+                    rq_pos += u.n;
+                    ++run_i;
+                    ++prof.run_fams;
+                    kick_tasks(false);
+                    continue;
                 }
             }
             const Rec &r = rqp[rq_pos];
@@ -1881,13 +2054,14 @@ struct dcr_ingest {
                 continue;
             }
             if (r.mi_type != 'Z') return stop(DCR_ERR_ATTRIBUTE, "'int' object has no attribute 'split'");
-            if (!fam.empty() && !same_code(r, *fam.front())) {
+            if (!fam.empty() && !same_code(wb, r, *fam.front())) {
                 const double tc = prof.on ? IngestProf::now() : 0;
-                const int c = queue_family();
+                const int c = queue_open_family();
                 if (prof.on) prof.complete += IngestProf::now() - tc;
                 if (c <= 0) return c;      // 0: batch full, the read stays unconsumed
                 fam.clear();
                 kick_tasks(false);
+                continue;                  // the read opens the next family, or a run of the table does
             }
             ++passed;
             ++records;
