@@ -14,6 +14,10 @@ The per-record work runs natively (libdcr_io.so, include/dcr_io.h):
   blocks on a worker pool; excluded reads and filtered families are copied
   through as stored.
 
+``--single_strand_output FILE`` (not a reference flag) also writes the four
+single-strand consensus reads of every written family, which the reference
+builds (``make_consensus_read(method="single_strand")`` :1564-1569) and drops.
+
 Batches are pipelined: a thread ingests batch k+1 while the device runs batch
 k and the main thread writes batch k-1.
 
@@ -78,6 +82,10 @@ def parse_args(argv):
     ap.add_argument("--device", required=False, default=0, type=int, help=argparse.SUPPRESS)
     # one process per GPU over ranges of whole families (sharded mode below)
     ap.add_argument("--gpus", required=False, default=1, type=int, help=argparse.SUPPRESS)
+    # not a reference flag: the four single-strand consensus reads of every
+    # written family (make_consensus_read method="single_strand", which the
+    # reference builds and drops) into a BAM of their own
+    ap.add_argument("--single_strand_output", required=False, default=None, type=str)
     return ap.parse_args(argv)
 
 
@@ -220,13 +228,34 @@ def gpu_inflate(device: int = 0):
     return got[0]
 
 
-def _as_backend(backend, params, device=0):
+def _as_backend(backend, params, device=0, ss_output=False):
+    """``ss_output``: this run also writes the single-strand records (a
+    property of the run, set on the backend each time: the default backend
+    is kept across runs)."""
     if backend is None:
-        return default_backend(params, device)
-    if hasattr(backend, "submit"):
-        return backend
-    from .stream import CallBackend
-    return CallBackend(backend, params)
+        be = default_backend(params, device)
+    elif hasattr(backend, "submit"):
+        be = backend
+    else:
+        from .stream import CallBackend
+        be = CallBackend(backend, params)
+    if hasattr(be, "ss_output"):
+        be.ss_output = ss_output
+    elif ss_output:
+        raise ValueError("this backend cannot produce the single-strand records")
+    return be
+
+
+OUTPUT_FORMAT_ERROR = ("ERROR: output file is not specified in the right format. \n Please specify the file name of a "
+                       "valid .bam file. Include the format in the file name.")      # :1491
+
+
+def _check_ss_output(args, say=True):
+    """--single_strand_output must name a .bam file, as -o must (:1488-1492)."""
+    if args.single_strand_output is not None and not args.single_strand_output.endswith(".bam"):
+        if say:
+            print(OUTPUT_FORMAT_ERROR)
+        raise ReferenceExit(1)
 
 
 def _raise_reference(kind: str, msg: str = ""):
@@ -240,9 +269,10 @@ def _raise_reference(kind: str, msg: str = ""):
 
 
 class _Driver:
-    def __init__(self, args, params, backend, ing, cons, excl, unproc):
+    def __init__(self, args, params, backend, ing, cons, excl, unproc, sscs=None):
+        """``sscs``: the writer of the single-strand records' file, or None."""
         self.args, self.params, self.backend = args, params, backend
-        self.ing, self.cons, self.excl, self.unproc = ing, cons, excl, unproc
+        self.ing, self.cons, self.excl, self.unproc, self.sscs = ing, cons, excl, unproc, sscs
         self.verbose = args.verbose
         # per-stage busy seconds and totals (bench.py --e2e reports them)
         self.trace = None          # optional [(stage, t0, t1)] (bench.py)
@@ -381,12 +411,20 @@ class _Driver:
                 self.cons.put_blocks(res.bgzf, res.record_bytes)
             elif fail_f:
                 self.cons.write(res.record_bytes_of(fail_f))
+            if self.sscs is not None:
+                # as `for r in single_consensus: write(r)` beside :1593-1594
+                if fail_f == F:
+                    self.sscs.put_blocks(res.ss_bgzf, res.ss_record_bytes)
+                elif fail_f:
+                    self.sscs.write(res.ss_record_bytes_of(fail_f))
             lens = res.ds_len[:2 * fail_f]
         else:
             ss, ds, rstat = res
             fail_f, kind, which = native_io.first_failure(hb, ss, ds, F, rstat)
             self._prints(hb, fail_f, kind, which, last_batch)
             self.cons.write_consensus(hb, ss, ds, fail_f)
+            if self.sscs is not None:
+                self.sscs.write_consensus_ss(hb, ss, fail_f)
             lens = np.ctypeslib.as_array(ctypes.cast(ds.len, ctypes.POINTER(ctypes.c_int32)), (2 * F,))[:2 * fail_f] \
                 if F else np.zeros(0, np.int32)
         st["batches"] += 1
@@ -430,6 +468,20 @@ class _Driver:
 
         first = [True]
 
+        def fill(hb):
+            """The next batch into ``hb``; a family larger than its capacities
+            gets a batch twice as large, and so on (batch boundaries, and so
+            --batch_reads, never change the outputs).  Returns the batch filled."""
+            while True:
+                try:
+                    self.ing.next(hb)
+                    return hb
+                except native_io.IOError_ as e:
+                    if "exceeds the batch capacities" not in str(e) or hb.reads >= (1 << 28):
+                        raise
+                hb = self.backend.host_batch(2 * hb.reads)
+                batches.append(hb)
+
         def ingest():
             try:
                 while not stop.is_set():
@@ -443,6 +495,7 @@ class _Driver:
                         # fills (batch boundaries never change the outputs); a
                         # family too large for it takes the full batch
                         first[0] = False
+                        hb0 = hb
                         caps = (hb.s.cap_fam, hb.s.cap_tab, hb.s.cap_reads, hb.s.cap_cigar, hb.s.cap_bases)
                         hb.s.cap_fam, hb.s.cap_tab = caps[0] // 8, caps[1] // 8
                         hb.s.cap_reads, hb.s.cap_cigar, hb.s.cap_bases = caps[2] // 8, caps[3] // 8, caps[4] // 8
@@ -452,12 +505,13 @@ class _Driver:
                             if "exceeds the batch capacities" not in str(e):
                                 raise
                             (hb.s.cap_fam, hb.s.cap_tab, hb.s.cap_reads, hb.s.cap_cigar, hb.s.cap_bases) = caps
-                            self.ing.next(hb)
+                            hb = fill(hb)
                         finally:
-                            (hb.s.cap_fam, hb.s.cap_tab, hb.s.cap_reads, hb.s.cap_cigar, hb.s.cap_bases) = caps
+                            s = hb0.s
+                            (s.cap_fam, s.cap_tab, s.cap_reads, s.cap_cigar, s.cap_bases) = caps
                     else:
                         first[0] = False
-                        self.ing.next(hb)
+                        hb = fill(hb)
                     t1 = time.perf_counter()
                     self.stats["ingest_s"] += t1 - t0
                     if self.trace is not None:
@@ -519,7 +573,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
         gpu_inflate(args.device)       # the GPU path reads its input through the device inflater too
     try:
         ing = native_io.Ingest(args.input_file, params.min_map_quality, params.min_reads, params.max_reads,
-                               params.min_base_quality, args.threads)
+                               params.min_base_quality, args.threads, ss_meta=args.single_strand_output is not None)
         if args.verbose:
             print(args.input_file, "has been read.")
     except Exception:
@@ -531,17 +585,19 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
     elif args.output_file.endswith(".bam"):
         consensus_filename = args.output_file
     else:
-        print("ERROR: output file is not specified in the right format. \n Please specify the file name of a "
-              "valid .bam file. Include the format in the file name.")
+        print(OUTPUT_FORMAT_ERROR)
         raise ReferenceExit(1)
-    be = _as_backend(backend, params, args.device)
-    cons, excl, unproc = _open_writers(
+    _check_ss_output(args)
+    ss_path = args.single_strand_output
+    be = _as_backend(backend, params, args.device, ss_path is not None)
+    cons, excl, unproc, *rest = _open_writers(
         [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
-         "%s_filteredfamilies.bam" % consensus_filename[:-4]], ing.header, args, ing)
+         "%s_filteredfamilies.bam" % consensus_filename[:-4]] + ([ss_path] if ss_path else []), ing.header, args, ing)
+    sscs = rest[0] if rest else None
     ing.set_rng_state(rng.getstate())
     t_open = time.perf_counter()
     try:
-        drv = _Driver(args, params, be, ing, cons, excl, unproc)
+        drv = _Driver(args, params, be, ing, cons, excl, unproc, sscs)
         if stats is not None and "trace" in stats:
             drv.trace = stats["trace"]
         try:
@@ -563,7 +619,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
             rng.setstate(ing.rng_state(rng.getstate()))
         finally:
             try:
-                _close_all(excl.close, unproc.close, cons.close)
+                _close_all(excl.close, unproc.close, cons.close, *((sscs.close,) if sscs else ()))
             finally:
                 t_wclose = time.perf_counter()
                 ing.close()
@@ -707,18 +763,20 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
     (optional): the ingest's state gate (native_io.Ingest.set_state_gate).
     ``header``: rank 0 writes the final files themselves, header first."""
     res = {"status": "ok", "exc_args": (), "calls": [], "counters": None, "stdout": "", "stats": {},
-           "sizes": [0, 0, 0]}
+           "sizes": [0] * len(parts)}
     out = io.StringIO()
     if backend is None:
         gpu_inflate(device)
     ing = native_io.Ingest(path, params.min_map_quality, params.min_reads, params.max_reads,
-                           params.min_base_quality, args.threads, rng_range[0], rng_range[1])
-    be = _as_backend(backend, params, device)
-    cons, excl, unproc = _open_writers(parts, header, args, ing)
+                           params.min_base_quality, args.threads, rng_range[0], rng_range[1],
+                           ss_meta=len(parts) > 3)
+    be = _as_backend(backend, params, device, len(parts) > 3)
+    cons, excl, unproc, *rest = _open_writers(parts, header, args, ing)
+    sscs = rest[0] if rest else None
     ing.set_rng_state(rng_state)
     if gate is not None:
         ing.set_state_gate(gate)
-    drv = _Driver(args, params, be, ing, cons, excl, unproc)
+    drv = _Driver(args, params, be, ing, cons, excl, unproc, sscs)
     drv.ends_at_eof = rng_range[1] == -1
     try:
         with contextlib.redirect_stdout(out):
@@ -735,7 +793,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
         res["stats"] = dict(drv.stats)
         res["stdout"] = out.getvalue()
         try:
-            _close_all(excl.close, unproc.close, cons.close)
+            _close_all(excl.close, unproc.close, cons.close, *((sscs.close,) if sscs else ()))
         finally:
             ing.close()
         res["sizes"] = [os.path.getsize(p) for p in parts]
@@ -955,15 +1013,16 @@ def _merge_parallel(dist, rank, finals, header, args, sizes, upto, parts):
     allocated (posix_fallocate) before it broadcasts the offsets; rank 0 then
     puts the BGZF EOF block at the end."""
     eof = len(_BGZF_EOF)
+    nf = len(finals)                         # 3, or 4 with the single-strand records' file
     if rank == 0:
-        for k in range(3):
+        for k in range(nf):
             if sizes[0][k] == 0:             # rank 0 never opened its writers: the header alone
                 w = native_io.BgzfWriter(finals[k], header, args.compression_level, args.threads)
                 w.close()
                 sizes[0][k] = os.path.getsize(finals[k])
 
     def ends_of(s0):
-        return [s0[k] - eof + sum(max(sizes[r][k] - eof, 0) for r in range(1, upto)) for k in range(3)]
+        return [s0[k] - eof + sum(max(sizes[r][k] - eof, 0) for r in range(1, upto)) for k in range(nf)]
     mapped = False
     if rank == 0 and upto > 1:
         # the finals' whole length allocated before any rank writes: the
@@ -971,7 +1030,7 @@ def _merge_parallel(dist, rank, finals, header, args, sizes, upto, parts):
         # block or the end of the file); a file system without fallocate
         # keeps the pwrite path
         mapped = True
-        for k, e in enumerate(ends_of([sizes[0][j] for j in range(3)])):
+        for k, e in enumerate(ends_of([sizes[0][j] for j in range(nf)])):
             fd = os.open(finals[k], os.O_RDWR)
             try:
                 start = sizes[0][k] - eof
@@ -981,11 +1040,11 @@ def _merge_parallel(dist, rank, finals, header, args, sizes, upto, parts):
                 mapped = False
             finally:
                 os.close(fd)
-    obj = [[sizes[0][k] for k in range(3)], mapped]
+    obj = [[sizes[0][k] for k in range(nf)], mapped]
     dist.broadcast_object_list(obj, src=0)
     s0, mapped = obj
     ends = ends_of(s0)
-    for k in range(3):
+    for k in range(nf):
         off = s0[k] - eof
         for r in range(1, upto):
             n = max(sizes[r][k] - eof, 0)
@@ -993,7 +1052,7 @@ def _merge_parallel(dist, rank, finals, header, args, sizes, upto, parts):
                 _write_part_at(parts[k], finals[k], n, off, mapped=mapped)
             off += n
     if rank == 0:
-        for k in range(3):
+        for k in range(nf):
             fd = os.open(finals[k], os.O_WRONLY)
             try:
                 os.pwrite(fd, _BGZF_EOF, ends[k])
@@ -1025,11 +1084,13 @@ def _main_sharded(args, params, backend, rng, stats, group):
         consensus_filename = args.output_file
     else:
         if rank == 0:
-            print("ERROR: output file is not specified in the right format. \n Please specify the file name of a "
-                  "valid .bam file. Include the format in the file name.")
+            print(OUTPUT_FORMAT_ERROR)
         raise ReferenceExit(1)
+    _check_ss_output(args, say=rank == 0)
     finals = [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
               "%s_filteredfamilies.bam" % consensus_filename[:-4]]
+    if args.single_strand_output is not None:
+        finals.append(args.single_strand_output)
     obj = [native_io.split_points(path, world, params) if rank == 0 else None,
            rng.getstate() if rank == 0 else None]
     dist.broadcast_object_list(obj, src=0)
@@ -1047,7 +1108,7 @@ def _main_sharded(args, params, backend, rng, stats, group):
     local = int(os.environ.get("LOCAL_RANK", rank))
     device = _rank_device(args, local) if backend is None else args.device
     empty = {"status": "ok", "exc_args": (), "calls": [], "counters": None, "stdout": "", "stats": {},
-             "sizes": [0, 0, 0]}
+             "sizes": [0] * len(finals)}
     result, used, rounds = empty, None, 0
     xch = _StateExchange(dist, rank, world, s0, path, params, mine, args.threads, args.batch_reads)
     done = False

@@ -219,9 +219,27 @@ struct WriterBufs {
     uint32_t *tok;
 };
 
+// The second stream of dcr_submit_write_ss: the single-strand records'
+// metadata, sizes and offsets, their record stream and its BGZF blocks
+// (k_deflate's slot, size and claim buffers of its second launch).
+struct WriterSsBufs {
+    int64_t B, nbm;         // the stream's bound in bytes and blocks (stream_bound_ss), set by the caller
+    unsigned gd;            // k_deflate workgroups
+    uint16_t *sub_flag;
+    int64_t *sub_mi, *sub_rx;
+    int64_t *rec_size, *rec_off, *scan;
+    uint8_t *stream, *slots;
+    int64_t *bsz, *boff;
+    uint8_t *comp;
+    int64_t *tot;
+    uint32_t *tok;
+};
+
 // F families, n_names bytes of names, a record stream of at most B bytes in
-// at most nbm blocks, gd k_deflate workgroups
-void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w) {
+// at most nbm blocks, gd k_deflate workgroups; with ws, the single-strand
+// stream's regions after them (the first stream's layout does not change)
+void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w,
+                 WriterSsBufs *ws = nullptr) {
     w.names = p.take<char>((size_t)n_names + 1);
     w.fam_code = p.take<int64_t>((size_t)F);
     w.fam_rx = p.take<int64_t>(2 * (size_t)F);
@@ -238,6 +256,21 @@ void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd
     w.comp = p.take<uint8_t>((size_t)nbm * dfl::kSlot);
     w.tot = p.take<int64_t>(4);
     w.tok = p.take<uint32_t>((size_t)gd * dfl::kTokWords);
+    if (!ws) return;
+    ws->sub_flag = p.take<uint16_t>(4 * (size_t)F);
+    ws->sub_mi = p.take<int64_t>(4 * (size_t)F);
+    ws->sub_rx = p.take<int64_t>(4 * (size_t)F);
+    ws->rec_size = p.take<int64_t>((size_t)(4 * F + 1));
+    ws->rec_off = p.take<int64_t>((size_t)(4 * F + 1));
+    ws->scan = (int64_t *)p.take<char>(
+        std::max(dcrw::scan_tmp_bytes((int)(4 * F + 1)), dcrw::scan_tmp_bytes((int)(ws->nbm + 1))));
+    ws->stream = p.take<uint8_t>((size_t)ws->B);
+    ws->slots = p.take<uint8_t>((size_t)ws->nbm * dfl::kSlot);
+    ws->bsz = p.take<int64_t>((size_t)(ws->nbm + 2));
+    ws->boff = p.take<int64_t>((size_t)(ws->nbm + 1));
+    ws->comp = p.take<uint8_t>((size_t)ws->nbm * dfl::kSlot);
+    ws->tot = p.take<int64_t>(4);
+    ws->tok = p.take<uint32_t>((size_t)ws->gd * dfl::kTokWords);
 }
 }  // namespace
 
@@ -273,8 +306,11 @@ struct dcr_ctx {
         DevBuf wbuf;              // device record writer: metadata, record stream, BGZF blocks
         int64_t *d_rec_off = nullptr;
         uint8_t *d_stream = nullptr, *d_comp = nullptr;
+        // the single-strand stream of dcr_submit_write_ss (writer_ss)
+        int64_t *d_ss_rec_off = nullptr;
+        uint8_t *d_ss_stream = nullptr, *d_ss_comp = nullptr;
         int64_t n_fam = 0;
-        bool writer = false;
+        bool writer = false, writer_ss = false;
         hipEvent_t ev_h2d = nullptr, ev_comp = nullptr, ev_d2h = nullptr;
         int *h_err = nullptr;     // pinned copy of the batch's capacity flag
         bool busy = false;
@@ -882,6 +918,7 @@ int dcr_submit(dcr_ctx *c, int slot, const dcr_batch *h, dcr_out *hss, dcr_out *
     HIP_TRY(download_outputs(&dout[1], hds, 2 * (int64_t)h->n_fam, h->ds_cols, c->s_d2h));
     HIP_TRY(hipEventRecord(S.ev_d2h, c->s_d2h));
     S.writer = false;
+    S.writer_ss = false;
     S.busy = true;
     return DCR_OK;
 }
@@ -919,8 +956,24 @@ static int64_t stream_bound(const dcr_batch *h, const dcr_wmeta *m) {
     return B;
 }
 
-int dcr_submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *m, dcr_wres *res) {
-    if (!c || !h || !m || !res) return fail(DCR_EARG, "NULL argument");
+// Upper bound of the formatted single-strand records of a batch
+// (dcr_writer.hip rec_size_ss): per column of the region at most 4 bytes of
+// CIGAR, 1.5 of sequence and quality and 7 + 7 of the two depth lists.
+static int64_t stream_bound_ss(const dcr_batch *h, const dcr_wmeta *m, const dcr_wmeta_ss *ms) {
+    int64_t B = 0;
+    for (int32_t f = 0; f < h->n_fam; ++f) {
+        const int64_t lc = (int64_t)std::strlen(m->names + m->fam_code[f]);
+        for (int s = 4 * f; s < 4 * f + 4; ++s)
+            B += 160 + lc + (int64_t)std::strlen(m->names + ms->sub_mi[s]) + (int64_t)std::strlen(m->names + ms->sub_rx[s]) +
+                 20 * (h->ss_col_off[s + 1] - h->ss_col_off[s]) + (h->sub_off[s + 1] - h->sub_off[s]);
+    }
+    return B;
+}
+
+// dcr_submit_write, and with ms / res_ss dcr_submit_write_ss: the same
+// launches and copies, then the single-strand stream's
+static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *m, const dcr_wmeta_ss *ms,
+                        dcr_wres *res, dcr_wres *res_ss) {
     dcr_ctx::Slot *Sp = nullptr;
     int rc = slot_open(c, slot, &Sp);
     if (rc) return rc;
@@ -938,11 +991,17 @@ int dcr_submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *
     const int64_t nbm = B / (int64_t)dfl::kMaxIn + 2;
     const unsigned gd = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nbm, (int64_t)c->n_cu * c->dfl_blocks));
     WriterBufs wb;
+    WriterSsBufs wsb{};
+    if (ms) {
+        wsb.B = stream_bound_ss(h, m, ms);
+        wsb.nbm = wsb.B / (int64_t)dfl::kMaxIn + 2;
+        wsb.gd = (unsigned)std::max<int64_t>(1, std::min<int64_t>(wsb.nbm, (int64_t)c->n_cu * c->dfl_blocks));
+    }
     Plan wsz;
-    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb);
+    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr);
     if (wsz.off > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wsz.off + wsz.off / 8));
     Plan wp{(char *)S.wbuf.p};
-    plan_writer(F, m->n_names, B, nbm, gd, wp, wb);
+    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr);
     // H2D: inputs and writer metadata on the copy stream
     HIP_TRY(upload_inputs(h, db, c->s_h2d));
     if (m->n_names) HIP_TRY(hipMemcpyAsync(wb.names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
@@ -950,6 +1009,11 @@ int dcr_submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *
         HIP_TRY(hipMemcpyAsync(wb.fam_code, m->fam_code, 8 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
         HIP_TRY(hipMemcpyAsync(wb.fam_rx, m->fam_rx, 16 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
         HIP_TRY(hipMemcpyAsync(wb.fam_tid, m->fam_tid, 4 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
+    }
+    if (ms && F) {
+        HIP_TRY(hipMemcpyAsync(wsb.sub_flag, ms->sub_flag, 8 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
+        HIP_TRY(hipMemcpyAsync(wsb.sub_mi, ms->sub_mi, 32 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
+        HIP_TRY(hipMemcpyAsync(wsb.sub_rx, ms->sub_rx, 32 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
     }
     if ((rc = slot_run(c, S, h, &db, dout))) return rc;
     // record writer
@@ -992,6 +1056,46 @@ int dcr_submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *
     dcrw::CompactArgs C{wb.slots, wb.bsz, wb.boff, wb.rec_off + 2 * F, wb.comp, wb.tot};
     hipLaunchKernelGGL(dcrw::k_compact, dim3(gd), dim3(256), 0, c->stream, C);
     HIP_TRY(hipGetLastError());
+    if (ms) {
+        // the single-strand stream: its own sizes, offsets and records
+        // (k_famfail's outcomes are shared), then k_deflate and k_compact again
+        dcrw::FmtSsArgs As{};
+        As.ss = dout[0];
+        As.sub_off = db.sub_off;
+        As.read_mapq = db.read_mapq;
+        As.ss_col_off = db.ss_col_off;
+        As.names = wb.names;
+        As.fam_code = wb.fam_code;
+        As.fam_tid = wb.fam_tid;
+        As.sub_flag = wsb.sub_flag;
+        As.sub_mi = wsb.sub_mi;
+        As.sub_rx = wsb.sub_rx;
+        As.n_fam = (int32_t)F;
+        As.fam_fail = wb.fam_fail;
+        As.rec_size = wsb.rec_size;
+        As.rec_off = wsb.rec_off;
+        As.stream = wsb.stream;
+        HIP_TRY(hipMemsetAsync(wsb.rec_size, 0, 8 * (size_t)(4 * F + 1), c->stream));
+        HIP_TRY(hipMemsetAsync(wsb.bsz, 0, 8 * (size_t)(wsb.nbm + 2), c->stream));
+        if (F) {
+            const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)c->n_cu * 8));
+            hipLaunchKernelGGL(dcrw::k_fmt_size_ss, dim3(g), dim3(256), 0, c->stream, As);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(dcrw::scan_excl_i64(wsb.rec_size, wsb.rec_off, (int)(4 * F + 1), wsb.scan, c->stream));
+            hipLaunchKernelGGL(dcrw::k_fmt_write_ss, dim3(g), dim3(256), 0, c->stream, As);
+            HIP_TRY(hipGetLastError());
+        } else {
+            HIP_TRY(hipMemsetAsync(wsb.rec_off, 0, 8, c->stream));
+        }
+        dcrw::DflArgs Ds{wsb.stream, wsb.rec_off + 4 * F, wsb.slots, wsb.bsz, wsb.tok, nullptr,
+                         (unsigned long long *)(wsb.bsz + wsb.nbm + 1)};
+        hipLaunchKernelGGL(dcrw::k_deflate, dim3(wsb.gd), dim3(dfl::kT), sizeof(dfl::Shared), c->stream, Ds);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(dcrw::scan_excl_i64(wsb.bsz, wsb.boff, (int)(wsb.nbm + 1), wsb.scan, c->stream));
+        dcrw::CompactArgs Cs{wsb.slots, wsb.bsz, wsb.boff, wsb.rec_off + 4 * F, wsb.comp, wsb.tot};
+        hipLaunchKernelGGL(dcrw::k_compact, dim3(wsb.gd), dim3(256), 0, c->stream, Cs);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipEventRecord(S.ev_comp, c->stream));
     // D2H of the per-family outcome and the totals on the second copy stream
     HIP_TRY(hipStreamWaitEvent(c->s_d2h, S.ev_comp, 0));
@@ -1000,13 +1104,44 @@ int dcr_submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *
         HIP_TRY(hipMemcpyAsync(res->ds_len, wb.ds_len, 8 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
     }
     HIP_TRY(hipMemcpyAsync(res->totals, wb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
+    if (ms) HIP_TRY(hipMemcpyAsync(res_ss->totals, wsb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
     HIP_TRY(hipEventRecord(S.ev_d2h, c->s_d2h));
     S.d_rec_off = wb.rec_off;
     S.d_stream = wb.stream;
     S.d_comp = wb.comp;
+    S.d_ss_rec_off = ms ? wsb.rec_off : nullptr;
+    S.d_ss_stream = ms ? wsb.stream : nullptr;
+    S.d_ss_comp = ms ? wsb.comp : nullptr;
     S.n_fam = F;
     S.writer = true;
+    S.writer_ss = ms != nullptr;
     S.busy = true;
+    return DCR_OK;
+}
+
+int dcr_submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *m, dcr_wres *res) {
+    if (!c || !h || !m || !res) return fail(DCR_EARG, "NULL argument");
+    return submit_write(c, slot, h, m, nullptr, res, nullptr);
+}
+
+int dcr_submit_write_ss(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmeta *m, const dcr_wmeta_ss *ms,
+                        dcr_wres *res, dcr_wres *res_ss) {
+    if (!c || !h || !m || !ms || !res || !res_ss) return fail(DCR_EARG, "NULL argument");
+    if (h->n_fam > 0 && (!ms->sub_flag || !ms->sub_mi || !ms->sub_rx))
+        return fail(DCR_EARG, "single-strand metadata missing");
+    return submit_write(c, slot, h, m, ms, res, res_ss);
+}
+
+// the tail of dcr_wait_write: a finished slot's compressed blocks into res->bgzf
+static int fetch_blocks(dcr_ctx *c, const uint8_t *d_comp, dcr_wres *res) {
+    const int64_t n = res->totals[0];
+    if (n > res->cap_bgzf) return fail(DCR_ECAPACITY, "BGZF output larger than cap_bgzf (see totals[0])");
+    if (n > 0) {
+        if (!c->ev_fetch) HIP_TRY(hipEventCreateWithFlags(&c->ev_fetch, hipEventDisableTiming | hipEventBlockingSync));
+        HIP_TRY(hipMemcpyAsync(res->bgzf, d_comp, (size_t)n, hipMemcpyDeviceToHost, c->s_fetch));
+        HIP_TRY(hipEventRecord(c->ev_fetch, c->s_fetch));
+        HIP_TRY(hipEventSynchronize(c->ev_fetch));
+    }
     return DCR_OK;
 }
 
@@ -1018,15 +1153,23 @@ int dcr_wait_write(dcr_ctx *c, int slot, dcr_wres *res) {
     HIP_TRY(hipEventSynchronize(S.ev_d2h));
     S.busy = false;
     if (*S.h_err) return fail(DCR_ECAPACITY, "a consensus needed more columns than its output region");
-    const int64_t n = res->totals[0];
-    if (n > res->cap_bgzf) return fail(DCR_ECAPACITY, "BGZF output larger than cap_bgzf (see totals[0])");
-    if (n > 0) {
-        if (!c->ev_fetch) HIP_TRY(hipEventCreateWithFlags(&c->ev_fetch, hipEventDisableTiming | hipEventBlockingSync));
-        HIP_TRY(hipMemcpyAsync(res->bgzf, S.d_comp, (size_t)n, hipMemcpyDeviceToHost, c->s_fetch));
-        HIP_TRY(hipEventRecord(c->ev_fetch, c->s_fetch));
-        HIP_TRY(hipEventSynchronize(c->ev_fetch));
-    }
-    return DCR_OK;
+    return fetch_blocks(c, S.d_comp, res);
+}
+
+int dcr_wait_write_ss(dcr_ctx *c, int slot, dcr_wres *res, dcr_wres *res_ss) {
+    if (!c || !res || !res_ss || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
+    dcr_ctx::Slot &S = c->slots[slot];
+    if (!S.busy || !S.writer || !S.writer_ss) return fail(DCR_EARG, "slot has no single-strand writer batch in flight");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(S.ev_d2h));
+    S.busy = false;
+    if (*S.h_err) return fail(DCR_ECAPACITY, "a consensus needed more columns than its output region");
+    // both streams are tried, so that after DCR_ECAPACITY the caller can
+    // tell from the two totals[0] which of them to fetch again
+    const int rc = fetch_blocks(c, S.d_comp, res);
+    if (rc != DCR_OK && rc != DCR_ECAPACITY) return rc;
+    const int rc_ss = fetch_blocks(c, S.d_ss_comp, res_ss);
+    return rc_ss != DCR_OK ? rc_ss : rc;
 }
 
 int dcr_slot_fetch(dcr_ctx *c, int slot, int what, int64_t off, int64_t n, void *dst) {
@@ -1042,8 +1185,19 @@ int dcr_slot_fetch(dcr_ctx *c, int slot, int what, int64_t off, int64_t n, void 
         if (n) HIP_TRY(hipMemcpy(dst, S.d_rec_off + off, 8 * (size_t)n, hipMemcpyDeviceToHost));
     } else if (what == 2) {
         if (n) HIP_TRY(hipMemcpy(dst, S.d_comp + off, (size_t)n, hipMemcpyDeviceToHost));
+    } else if (what >= 3 && what <= 5) {
+        if (!S.writer_ss) return fail(DCR_EARG, "slot holds no single-strand writer batch");
+        if (what == 3) {
+            if (n) HIP_TRY(hipMemcpy(dst, S.d_ss_stream + off, (size_t)n, hipMemcpyDeviceToHost));
+        } else if (what == 4) {
+            if (off + n > 4 * S.n_fam + 1) return fail(DCR_EARG, "record offsets out of range");
+            if (n) HIP_TRY(hipMemcpy(dst, S.d_ss_rec_off + off, 8 * (size_t)n, hipMemcpyDeviceToHost));
+        } else {
+            if (n) HIP_TRY(hipMemcpy(dst, S.d_ss_comp + off, (size_t)n, hipMemcpyDeviceToHost));
+        }
     } else {
-        return fail(DCR_EARG, "what must be 0 (record bytes), 1 (record offsets) or 2 (BGZF blocks)");
+        return fail(DCR_EARG, "what must be 0 (record bytes), 1 (record offsets), 2 (BGZF blocks) or 3 to 5 "
+                              "(the same of the single-strand stream)");
     }
     return DCR_OK;
 }

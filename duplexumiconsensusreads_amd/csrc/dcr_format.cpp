@@ -353,6 +353,119 @@ size_t record_bound(const Ctx &c, int32_t f, int j, size_t l_code) {
     return n;
 }
 
+// one single-strand record (subfamily k of processed family f): the record
+// make_consensus_read(method="single_strand") returns (:1352-1384), tags of
+// add_tags (:1054-1073); mate fields stay unset (-1, -1, 0)
+void format_record_ss(const Ctx &c, int32_t f, int k, const char *code, size_t l_code, Buf &o) {
+    static const char *const kSub[4] = {"_A1", "_B2", "_B1", "_A2"};   // get_consensus_id (:909-920)
+    const dcr_host_batch *hb = c.hb;
+    const dcr_fmt_out *ss = c.ss;
+    const int32_t s = 4 * f + k;
+    const int32_t pos = ss->pos[s], len = ss->len[s], tid = hb->fam_tid[f];
+    const int64_t ro = hb->ss_col_off[s];
+    const size_t rec0 = o.n;
+    o.u32(0);                                        // block_size
+    o.u32((uint32_t)tid);
+    o.u32((uint32_t)pos);
+    o.b((uint8_t)(16 + l_code + 3 + 1));             // "consensus_family" code _XX NUL
+    o.b((uint8_t)(ss->mapq[s] & 0xff));
+    int64_t rl = 0;
+    const uint32_t *cg = ss->cigar + ro;
+    const int32_t nc = ss->n_cig[s];
+    for (int32_t i = 0; i < nc; ++i) {
+        const uint32_t op = cg[i] & 15;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += cg[i] >> 4;
+    }
+    o.u16(pos >= 0 ? (uint32_t)reg2bin(pos, pos + (rl > 0 ? rl : 1)) : 4680u);
+    o.u16((uint32_t)nc);
+    o.u16(hb->sub_flag[s]);                          // get_consensus_flag (:957-958): read0's
+    o.u32((uint32_t)len);
+    o.u32(0xffffffffu);                              // next_refID, next_pos -1; tlen 0
+    o.u32(0xffffffffu);
+    o.u32(0);
+    o.str("consensus_family");
+    o.raw(code, l_code);
+    o.str(kSub[k]);
+    o.b(0);
+    for (int32_t i = 0; i < nc; ++i) o.u32(cg[i]);
+    const uint8_t *sq = ss->seq + ro;
+    for (int32_t i = 0; i + 1 < len; i += 2) o.b((uint8_t)((kNt.code[sq[i]] << 4) | kNt.code[sq[i + 1]]));
+    if (len & 1) o.b((uint8_t)(kNt.code[sq[len - 1]] << 4));
+    o.raw(ss->qual + ro, (size_t)len);
+    z_begin(o, "MI");
+    o.str(hb->names + hb->sub_mi[s]);
+    o.b(0);
+    z_begin(o, "RX");
+    o.str(hb->names + hb->sub_rx[s]);
+    o.b(0);
+    u8_array(o, "sQ", hb->read_mapq + hb->sub_off[s], hb->sub_off[s + 1] - hb->sub_off[s]);
+    list_text(o, "sd", ss->d + ro, ss->n_de[s]);
+    int_tag(o, "sD", ss->D[s]);
+    int_tag(o, "sM", ss->M[s]);
+    list_text(o, "se", ss->e + ro, ss->n_de[s]);
+    float_tag(o, "sE", ss->E[s]);
+    wr32(o.v.data() + rec0, (uint32_t)(o.n - rec0 - 4));
+}
+
+size_t record_bound_ss(const Ctx &c, int32_t f, int k, size_t l_code) {
+    const int32_t s = 4 * f + k;
+    size_t n = 36 + 16 + l_code + 4 + 4 * (size_t)c.ss->n_cig[s] + (size_t)c.ss->len[s] * 2;
+    n += 8 + std::strlen(c.hb->names + c.hb->sub_mi[s]) + std::strlen(c.hb->names + c.hb->sub_rx[s]);
+    n += 8 + (size_t)(c.hb->sub_off[s + 1] - c.hb->sub_off[s]);
+    n += 16 + 8 * 2 * (size_t)c.ss->n_de[s] + 64;
+    n += 3 * 8 + 32;
+    return n;
+}
+
+// Families [0, n_fam) in chunks, each formatted (fmt(f, code, l_code, buf)
+// appends the family's records) and deflated by one task into its own run of
+// BGZF blocks (a record may span blocks), written in order.
+template <typename Fmt>
+int write_chunked(dcr_bgzw *w, const dcr_host_batch *hb, int32_t n_fam, Fmt fmt) {
+    const int64_t *code_of = hb->fam_code;
+    // pending bytes first (blocks stay in order)
+    if (w->n_in) {
+        if (!w->flush(w->n_in)) { w->bad = true; return DCR_IO_EFILE; }
+        w->n_in = 0;
+    }
+    const int32_t chunk = 128;
+    const int32_t nch = (n_fam + chunk - 1) / chunk;
+    const int32_t group = std::max(1, 4 * w->pl().size());
+    struct Task { Buf raw; std::vector<uint8_t> comp; size_t n_comp = 0; };
+    std::vector<Task> tasks((size_t)std::min(nch, group));
+    const int lvl = w->level;
+    for (int32_t g0 = 0; g0 < nch; g0 += group) {
+        const int32_t g1 = std::min(nch, g0 + group);
+        const bool ok = w->pl().run((size_t)(g1 - g0), [&](size_t gi) {
+            Task &t = tasks[gi];
+            Buf &o = t.raw;
+            o.n = 0;
+            const int32_t f0 = (g0 + (int32_t)gi) * chunk, f1 = std::min(n_fam, f0 + chunk);
+            for (int32_t f = f0; f < f1; ++f) {
+                const char *code = hb->names + code_of[f];
+                fmt(f, code, std::strlen(code), o);
+            }
+            const size_t nb = (o.n + kBlockData - 1) / kBlockData;
+            if (t.comp.size() < nb * 0x10000) t.comp.resize(nb * 0x10000);
+            t.n_comp = 0;
+            for (size_t b = 0; b < nb; ++b) {
+                const size_t off = b * kBlockData, len = std::min(kBlockData, o.n - off);
+                const size_t cl = bgzf_block(o.v.data() + off, len, lvl, t.comp.data() + t.n_comp);
+                if (!cl) return false;
+                t.n_comp += cl;
+            }
+            return true;
+        });
+        if (!ok) { w->bad = true; return fail(DCR_IO_EFILE, "BGZF block failed to deflate"); }
+        for (int32_t gi = 0; gi < g1 - g0; ++gi)
+            if (!w->put_compressed(tasks[(size_t)gi].comp.data(), tasks[(size_t)gi].n_comp, tasks[(size_t)gi].raw.n)) {
+                w->bad = true;
+                return DCR_IO_EFILE;
+            }
+    }
+    return DCR_IO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -450,55 +563,28 @@ int dcr_fmt_write(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, 
                   int32_t n_fam) {
     if (!w || !hb || !ss || !ds || n_fam < 0 || n_fam > hb->n_fam) return fail(DCR_IO_EARG, "bad arguments");
     if (w->bad) return fail(DCR_IO_EFILE, "writer failed earlier");
-    const int64_t *code_of = hb->fam_code;
     const Ctx c{hb, ss, ds};
-    // pending bytes first (blocks stay in order)
-    if (w->n_in) {
-        if (!w->flush(w->n_in)) { w->bad = true; return DCR_IO_EFILE; }
-        w->n_in = 0;
-    }
-    // chunks of families, each formatted and deflated by one task into its
-    // own run of BGZF blocks (a record may span blocks), written in order
-    const int32_t chunk = 128;
-    const int32_t nch = (n_fam + chunk - 1) / chunk;
-    const int32_t group = std::max(1, 4 * w->pl().size());
-    struct Task { Buf raw; std::vector<uint8_t> comp; size_t n_comp = 0; };
-    std::vector<Task> tasks((size_t)std::min(nch, group));
-    const int lvl = w->level;
-    for (int32_t g0 = 0; g0 < nch; g0 += group) {
-        const int32_t g1 = std::min(nch, g0 + group);
-        const bool ok = w->pl().run((size_t)(g1 - g0), [&](size_t gi) {
-            Task &t = tasks[gi];
-            Buf &o = t.raw;
-            o.n = 0;
-            const int32_t f0 = (g0 + (int32_t)gi) * chunk, f1 = std::min(n_fam, f0 + chunk);
-            for (int32_t f = f0; f < f1; ++f) {
-                const char *code = hb->names + code_of[f];
-                const size_t lc = std::strlen(code);
-                for (int j = 0; j < 2; ++j) {
-                    o.reserve(record_bound(c, f, j, lc));
-                    format_record(c, f, j, code, lc, o);
-                }
-            }
-            const size_t nb = (o.n + kBlockData - 1) / kBlockData;
-            if (t.comp.size() < nb * 0x10000) t.comp.resize(nb * 0x10000);
-            t.n_comp = 0;
-            for (size_t b = 0; b < nb; ++b) {
-                const size_t off = b * kBlockData, len = std::min(kBlockData, o.n - off);
-                const size_t cl = bgzf_block(o.v.data() + off, len, lvl, t.comp.data() + t.n_comp);
-                if (!cl) return false;
-                t.n_comp += cl;
-            }
-            return true;
-        });
-        if (!ok) { w->bad = true; return fail(DCR_IO_EFILE, "BGZF block failed to deflate"); }
-        for (int32_t gi = 0; gi < g1 - g0; ++gi)
-            if (!w->put_compressed(tasks[(size_t)gi].comp.data(), tasks[(size_t)gi].n_comp, tasks[(size_t)gi].raw.n)) {
-                w->bad = true;
-                return DCR_IO_EFILE;
-            }
-    }
-    return DCR_IO_OK;
+    return write_chunked(w, hb, n_fam, [&](int32_t f, const char *code, size_t lc, Buf &o) {
+        for (int j = 0; j < 2; ++j) {
+            o.reserve(record_bound(c, f, j, lc));
+            format_record(c, f, j, code, lc, o);
+        }
+    });
+}
+
+int dcr_fmt_write_ss(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, int32_t n_fam) {
+    if (!w || !hb || !ss || n_fam < 0 || n_fam > hb->n_fam) return fail(DCR_IO_EARG, "bad arguments");
+    if (!hb->sub_flag || !hb->sub_mi || !hb->sub_rx)
+        return fail(DCR_IO_EARG, "the batch carries no single-strand metadata (DCR_INGEST_SS_META)");
+    if (!ss->pos || !ss->n_cig || !ss->cigar) return fail(DCR_IO_EARG, "single-strand pos / n_cig / cigar missing");
+    if (w->bad) return fail(DCR_IO_EFILE, "writer failed earlier");
+    const Ctx c{hb, ss, nullptr};
+    return write_chunked(w, hb, n_fam, [&](int32_t f, const char *code, size_t lc, Buf &o) {
+        for (int k = 0; k < 4; ++k) {
+            o.reserve(record_bound_ss(c, f, k, lc));
+            format_record_ss(c, f, k, code, lc, o);
+        }
+    });
 }
 
 }  // extern "C"

@@ -1544,6 +1544,29 @@ struct dcr_ingest {
         return S;
     }
 
+    // DCR_INGEST_SS_META: the batch takes the single-strand records' metadata
+    bool ss_meta(const dcr_host_batch *b) const {
+        return (cfg.flags & DCR_INGEST_SS_META) && b->sub_flag && b->sub_mi && b->sub_rx;
+    }
+    // Arena bytes of that metadata (reserve_family: MI and RX of each
+    // subfamily's read0).  A family that samples is reserved from the sample,
+    // not yet drawn: four times its longest MI and RX bound any draw.
+    int64_t ss_names_need(const RecList &fr, size_t n, const FamSum &S, bool sampled) const {
+        if (!ss_meta(hb)) return 0;
+        if (sampled) {
+            int64_t l_mi = 0, l_rx = 0;
+            for (size_t i = 0; i < n; ++i) {
+                l_mi = std::max<int64_t>(l_mi, fr[i]->l_mi);
+                l_rx = std::max<int64_t>(l_rx, fr[i]->l_rx);
+            }
+            return 4 * (l_mi + 1 + l_rx + 1);
+        }
+        int64_t need = 0;
+        for (int k = 0; k < 4; ++k)
+            need += S.first[k] ? (int64_t)S.first[k]->l_mi + 1 + S.first[k]->l_rx + 1 : 2;
+        return need;
+    }
+
     // Is there room in the batch for the family of first record r0, all its reads counted
     // (the bound also of a family that samples, tested before any draw)?
     // Names: reserve_family writes the code and two RX strings, those of the
@@ -1554,12 +1577,12 @@ struct dcr_ingest {
     // yet drawn here, but reserved only after check_family: every RX is then
     // the first record's or its swapped halves, no longer than it.  Twice the
     // longest of the three covers both.
-    bool family_fits(const FamSum &S, const Rec &r0) const {
+    bool family_fits(const FamSum &S, const Rec &r0, int64_t ss_names) const {
         const dcr_host_batch *b = hb;
         int64_t l_rx = r0.l_rx;
         for (int k = 0; k < 4; k += 2)
             if (S.first[k]) l_rx = std::max<int64_t>(l_rx, S.first[k]->l_rx);
-        const int64_t names_need = (int64_t)r0.l_code + 1 + 2 * (l_rx + 1) + 64 * 2;
+        const int64_t names_need = (int64_t)r0.l_code + 1 + 2 * (l_rx + 1) + 64 * 2 + ss_names;
         return b->n_tab < b->cap_tab && b->n_fam < b->cap_fam && b->n_reads + S.n <= b->cap_reads &&
                b->n_bases + S.nb <= b->cap_bases && b->n_cigar + S.nc <= b->cap_cigar &&
                b->n_names + names_need <= b->cap_names && b->n_side_filt + S.bytes <= b->cap_side;
@@ -1639,6 +1662,15 @@ struct dcr_ingest {
             if (!r) b->fam_rx[2 * f + j] = put_name("", 0);
             else b->fam_rx[2 * f + j] = put_name(rx_of(*r), r->l_rx);
         }
+        // single-strand record metadata: flag, whole MI and RX of each
+        // subfamily's read0 (get_consensus_flag :957-958, add_tags :1057-1058)
+        if (ss_meta(b))
+            for (int k = 0; k < 4; ++k) {
+                const Rec *r = S.first[k];
+                b->sub_flag[4 * f + k] = r ? r->flag : 0;
+                b->sub_mi[4 * f + k] = r ? put_name((const char *)at(*r, r->o_mi), r->l_mi) : put_name("", 0);
+                b->sub_rx[4 * f + k] = r ? put_name(rx_of(*r), r->l_rx) : put_name("", 0);
+            }
         ++processed;
         return T;
     }
@@ -1715,7 +1747,7 @@ struct dcr_ingest {
              tasks.size() == tasks.capacity()) &&
             flush_tasks() < 0)
             return -1;
-        if (!family_fits(S, r0)) {
+        if (!family_fits(S, r0, ss_names_need(fr, n, S, sampled != 0))) {
             if (b->n_tab == 0 && b->n_side_exc == 0) {
                 if (flush_tasks() < 0) return -1;
                 return fail_capacity("one family exceeds the batch capacities");

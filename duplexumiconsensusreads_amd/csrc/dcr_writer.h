@@ -25,6 +25,24 @@ struct FmtArgs {
     uint8_t *stream;                // formatted records
 };
 
+// the single-strand records' writer (k_fmt_size_ss / k_fmt_write_ss)
+struct FmtSsArgs {
+    dcr_out ss;                     // device kernel outputs
+    const int32_t *sub_off;         // [4F+1]
+    const uint8_t *read_mapq;
+    const int64_t *ss_col_off;
+    const char *names;
+    const int64_t *fam_code;        // [F]
+    const int32_t *fam_tid;         // [F]
+    const uint16_t *sub_flag;       // [4F] read0's flag
+    const int64_t *sub_mi, *sub_rx; // [4F] names offsets of read0's MI / RX
+    int32_t n_fam;
+    const int32_t *fam_fail;        // [F] from k_famfail
+    int64_t *rec_size;              // [4F+1] (the last one 0: the scan's total)
+    int64_t *rec_off;               // [4F+1]
+    uint8_t *stream;                // formatted records
+};
+
 struct DflArgs {
     const uint8_t *stream;
     const int64_t *stream_bytes;    // device scalar (rec_off[2F])
@@ -47,6 +65,8 @@ struct CompactArgs {
 __global__ void k_famfail(FmtArgs A);
 __global__ void k_fmt_size(FmtArgs A);
 __global__ void k_fmt_write(FmtArgs A);
+__global__ void k_fmt_size_ss(FmtSsArgs A);
+__global__ void k_fmt_write_ss(FmtSsArgs A);
 __global__ void k_deflate(DflArgs D);
 __global__ void k_compact(CompactArgs C);
 

@@ -1,7 +1,9 @@
 // dcr_writer.hip — the record writer on the GPU: the two duplex BAM records
 // of every family of a batch formatted straight from the kernel outputs in
 // HBM, the failure scan, and the BGZF compression of the record stream
-// (dcr_deflate.h), so that only compressed blocks cross PCIe.
+// (dcr_deflate.h), so that only compressed blocks cross PCIe.  On request
+// (dcr_submit_write_ss) also the four single-strand records of every family,
+// as a second record stream compressed by the same kernels.
 //
 // Reference (/root/reference/DuplexUMIConsensusReads.py): record fields
 // make_consensus_read :1352-1384, names / flags :892-968, duplex tags
@@ -293,6 +295,130 @@ __global__ __launch_bounds__(256) void k_fmt_write(FmtArgs A) {
         Rec r;
         rec_setup(A, (int32_t)k, r);
         rec_write(A, r, A.stream + o, (uint32_t)n);
+    }
+}
+
+// ---- the single-strand records (dcr_submit_write_ss): record s = 4f + k is
+// what make_consensus_read(method="single_strand") returns for subfamily k
+// (A1 B2 B1 A2) of family f (:1352-1384): read0's flag, no mate fields, tags
+// MI RX sQ sd sD sM se sE (add_tags :1054-1073).  The layout is
+// dcr_format.cpp's format_record_ss.
+struct RecSs {
+    int32_t s, L, nc, tid, pos, mapq, r0, r1, nde;
+    int64_t ro;
+    const char *code, *mi, *rx;
+    uint32_t lc, lmi, lrx;
+};
+
+__device__ void rec_setup_ss(const FmtSsArgs &A, int32_t s, RecSs &r) {
+    const int32_t f = s >> 2;
+    r.s = s;
+    r.L = A.ss.len[s];
+    r.nc = A.ss.n_cig[s];
+    r.tid = A.fam_tid[f];
+    r.pos = A.ss.pos[s];
+    r.mapq = A.ss.mapq[s];
+    r.nde = A.ss.n_de[s];
+    r.ro = A.ss_col_off[s];
+    r.r0 = A.sub_off[s];
+    r.r1 = A.sub_off[s + 1];
+    r.code = A.names + A.fam_code[f];
+    r.mi = A.names + A.sub_mi[s];
+    r.rx = A.names + A.sub_rx[s];
+    r.lc = dstrlen(r.code);
+    r.lmi = dstrlen(r.mi);
+    r.lrx = dstrlen(r.rx);
+}
+
+__device__ uint32_t rec_size_ss(const FmtSsArgs &A, const RecSs &r) {
+    const dcr_out &ss = A.ss;
+    uint32_t n = 36 + 16 + r.lc + 3 + 1 + 4u * (uint32_t)r.nc + (uint32_t)((r.L + 1) >> 1) + (uint32_t)r.L;
+    n += 3 + r.lmi + 1 + 3 + r.lrx + 1;                      // MI, RX
+    n += 8 + (uint32_t)(r.r1 - r.r0);                        // sQ
+    n += 6 + list_body(ss.d + r.ro, r.nde) + 6 + list_body(ss.e + r.ro, r.nde);
+    n += int_tag_bytes(ss.D[r.s]) + int_tag_bytes(ss.M[r.s]) + 7;
+    return n;
+}
+
+__device__ void rec_write_ss(const FmtSsArgs &A, const RecSs &r, uint8_t *o, uint32_t total) {
+    const dcr_out &ss = A.ss;
+    Out w{o, 0};
+    w.u32(total - 4);
+    w.u32((uint32_t)r.tid);
+    w.u32((uint32_t)r.pos);
+    w.b1(16 + r.lc + 3 + 1);
+    w.b1((uint32_t)(r.mapq & 0xff));
+    const uint32_t *cg = ss.cigar + r.ro;
+    int64_t rl = 0;
+    if (lane_id() == 0)
+        for (int32_t i = 0; i < r.nc; ++i) {
+            const uint32_t op = cg[i] & 15;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += cg[i] >> 4;
+        }
+    w.u16(r.pos >= 0 ? (uint32_t)reg2bin(r.pos, r.pos + (rl > 0 ? rl : 1)) : 4680u);
+    w.u16((uint32_t)r.nc);
+    w.u16(A.sub_flag[r.s]);
+    w.u32((uint32_t)r.L);
+    w.u32(0xffffffffu);
+    w.u32(0xffffffffu);
+    w.u32(0);
+    w.str("consensus_family", 16);
+    w.str(r.code, r.lc);
+    const int k = r.s & 3;
+    w.str(k == 0 ? "_A1" : k == 1 ? "_B2" : k == 2 ? "_B1" : "_A2", 3);
+    w.b1(0);
+    for (int32_t i = lane_id(); i < r.nc; i += kW) {
+        const uint32_t v = cg[i];
+        for (int b = 0; b < 4; ++b) o[w.p + 4 * i + b] = (uint8_t)(v >> (8 * b));
+    }
+    w.p += 4u * (uint32_t)r.nc;
+    const uint8_t *sq = ss.seq + r.ro;
+    const int32_t nb = (r.L + 1) >> 1;
+    for (int32_t i = lane_id(); i < nb; i += kW) {
+        const uint8_t hi = nt_code(sq[2 * i]);
+        const uint8_t lo = (2 * i + 1 < r.L) ? nt_code(sq[2 * i + 1]) : 0;
+        o[w.p + i] = (uint8_t)((hi << 4) | lo);
+    }
+    w.p += (uint32_t)nb;
+    w.bytes(ss.qual + r.ro, (uint32_t)r.L);
+    w.tag('M', 'I', 'Z');
+    w.str(r.mi, r.lmi);
+    w.b1(0);
+    w.tag('R', 'X', 'Z');
+    w.str(r.rx, r.lrx);
+    w.b1(0);
+    w.tag('s', 'Q', 'B'); w.b1('C'); w.u32((uint32_t)(r.r1 - r.r0)); w.bytes(A.read_mapq + r.r0, (uint32_t)(r.r1 - r.r0));
+    w.list('s', 'd', ss.d + r.ro, r.nde);
+    w.int_tag('s', 'D', ss.D[r.s]);
+    w.int_tag('s', 'M', ss.M[r.s]);
+    w.list('s', 'e', ss.e + r.ro, r.nde);
+    w.float_tag('s', 'E', ss.E[r.s]);
+}
+
+// one wave per single-strand record; records of failing families get size 0
+__global__ __launch_bounds__(256) void k_fmt_size_ss(FmtSsArgs A) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;
+    const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
+    for (int64_t s = wave; s < 4LL * A.n_fam; s += nw) {
+        uint32_t n = 0;
+        if (A.fam_fail[s >> 2] == 0) {
+            RecSs r;
+            rec_setup_ss(A, (int32_t)s, r);
+            n = rec_size_ss(A, r);
+        }
+        if (lane_id() == 0) A.rec_size[s] = n;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fmt_write_ss(FmtSsArgs A) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;
+    const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
+    for (int64_t s = wave; s < 4LL * A.n_fam; s += nw) {
+        const int64_t o = A.rec_off[s], n = A.rec_off[s + 1] - o;
+        if (n == 0) continue;
+        RecSs r;
+        rec_setup_ss(A, (int32_t)s, r);
+        rec_write_ss(A, r, A.stream + o, (uint32_t)n);
     }
 }
 

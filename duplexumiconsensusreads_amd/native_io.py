@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("DCR_IO_LIB", os.path.join(HERE, "libdcr_io.so"))   # 
 _i32, _i64, _vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
 
 END_FULL, END_EOF, END_ERROR = 0, 1, 2
-INGEST_HOST_INFLATE = 1                  # dcr_ingest_cfg.flags
+INGEST_HOST_INFLATE, INGEST_SS_META = 1, 2       # dcr_ingest_cfg.flags
 ERR_NAMES = {1: "exit", 2: "TypeError", 3: "IndexError", 4: "ValueError", 5: "AttributeError"}
 FAM_PROCESSED, FAM_FILTERED = 0, 1
 FAIL_NAMES = {1: "IndexError", 2: "TypeError", 3: "ValueError", 4: "OverflowError", 5: "exit",
@@ -44,7 +44,10 @@ _HB_ARRAYS = [
     ("tab_kind", np.int32, "t"), ("tab_proc", np.int32, "t"), ("tab_sampled", np.int32, "t"),
     ("tab_code", np.int64, "t"), ("tab_exc_cut", np.int64, "t"), ("tab_filt_cut", np.int64, "t"),
     ("names", np.uint8, "n"), ("side_exc", np.uint8, "s"), ("side_filt", np.uint8, "s"),
+    ("sub_flag", np.uint16, "4f"), ("sub_mi", np.int64, "4f"), ("sub_rx", np.int64, "4f"),
 ]
+# the single-strand records' metadata: allocated (else NULL) for HostBatch(ss_meta=True)
+_SS_META = ("sub_flag", "sub_mi", "sub_rx")
 
 
 class HostBatchStruct(ctypes.Structure):
@@ -99,6 +102,7 @@ def load():
             "dcr_bgzw_sizes": (_i32, [_vp, _vp]),
             "dcr_fmt_scan": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
             "dcr_fmt_write": (_i32, [_vp, _vp, _vp, _vp, _i32]),
+            "dcr_fmt_write_ss": (_i32, [_vp, _vp, _vp, _i32]),
             "dcr_synth_write": (_i32, [_vp, _vp, _i32]),
             "dcr_deflate_emulate": (_i64, [_vp, _i64, _vp]),
             "dcr_deflate_lengths_ab": (_i32, [_vp, _i32, _vp, _vp]),
@@ -134,21 +138,26 @@ class HostBatch:
     single allocation (``alloc(nbytes) -> uint8 array``; pinned host memory
     on the GPU path)."""
 
-    def __init__(self, reads=1 << 20, avg_len=160, side_bytes=64 << 20, alloc=numpy_alloc):
+    def __init__(self, reads=1 << 20, avg_len=160, side_bytes=64 << 20, alloc=numpy_alloc, ss_meta=False):
+        """``ss_meta``: with the arrays of the single-strand records' metadata
+        (an ingest opened with ``ss_meta`` fills them) and an arena sized for
+        their strings."""
         self.reads = reads
+        self.ss_meta = ss_meta
         # a processed family holds at least one read per subfamily (min_reads
         # >= 1); a batch simply ends early when a table fills first
         f = max(reads // 4 + 16, 16)
         t = 2 * f
         caps = {"r": reads, "f": f, "4f": 4 * f, "4f1": 4 * f + 1, "2f": 2 * f, "2f1": 2 * f + 1, "t": t,
-                "c": 8 * reads, "b": avg_len * reads, "n": 96 * t + (1 << 16), "s": side_bytes}
+                "c": 8 * reads, "b": avg_len * reads, "n": 96 * t + (128 * 4 * f if ss_meta else 0) + (1 << 16),
+                "s": side_bytes}
         # pinned: what crosses PCIe (the dcr_batch arrays and the writer's
         # metadata); the family table and the side-file records stay host-only
         host_only = {"side_exc", "side_filt", "tab_kind", "tab_proc", "tab_sampled", "tab_code", "tab_exc_cut",
                      "tab_filt_cut"}
         lay, off = [], 0
         for name, dt, ln in _HB_ARRAYS:
-            if name in host_only:
+            if name in host_only or (name in _SS_META and not ss_meta):
                 continue
             nb = np.dtype(dt).itemsize * caps[ln]
             off = (off + 255) & ~255
@@ -242,13 +251,14 @@ class Ingest:
     """dcr_ingest: a BAM opened for batched reading."""
 
     def __init__(self, path, min_map_quality=20, min_reads=1, max_reads=100, min_base_quality=20, n_threads=0,
-                 start_voff=0, end_voff=-1, host_inflate=False):
+                 start_voff=0, end_voff=-1, host_inflate=False, ss_meta=False):
         """``start_voff`` / ``end_voff``: a range of whole families
         (split_points); the header is then empty.  ``host_inflate``: the host
-        inflate pool even when a GPU inflate hook is set."""
+        inflate pool even when a GPU inflate hook is set.  ``ss_meta``: fill
+        the single-strand records' metadata of batches that carry its arrays."""
         lib = load()
         cfg = IngestCfg(min_map_quality, min_reads, max_reads, min_base_quality, n_threads,
-                        INGEST_HOST_INFLATE if host_inflate else 0)
+                        (INGEST_HOST_INFLATE if host_inflate else 0) | (INGEST_SS_META if ss_meta else 0))
         if start_voff == 0 and end_voff == -1:
             self._h = lib.dcr_ingest_open(os.fsencode(path), ctypes.byref(cfg))
         else:
@@ -368,6 +378,11 @@ class BgzfWriter:
         if n_fam and load().dcr_fmt_write(self._h, ctypes.byref(hb.s), ctypes.byref(ss), ctypes.byref(ds),
                                           n_fam) != 0:
             raise _err("consensus write")
+
+    def write_consensus_ss(self, hb: HostBatch, ss: FmtOut, n_fam: int):
+        """The four single-strand records of families [0, n_fam) (dcr_fmt_write_ss)."""
+        if n_fam and load().dcr_fmt_write_ss(self._h, ctypes.byref(hb.s), ctypes.byref(ss), n_fam) != 0:
+            raise _err("single-strand consensus write")
 
     def write_synthetic(self, packed, umis, fam_id0=0, tid=0, n_threads=0):
         """Records of every family of ``packed`` (dcr_synth_write)."""

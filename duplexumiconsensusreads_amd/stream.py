@@ -21,8 +21,10 @@ from . import native_io
 from .batch import DcrOut, OUT_COLS, OUT_SCALARS
 
 # fields of the single-strand results the writer reads (dcr_fmt_out); pos,
-# n_cig and cigar of single-strand records stay on the device
+# n_cig and cigar of single-strand records stay on the device unless the
+# single-strand records themselves are written (SS_FIELDS_FULL)
 SS_FIELDS = ("status", "mapq", "len", "n_de", "D", "M", "E", "seq", "qual", "d", "e")
+SS_FIELDS_FULL = SS_FIELDS + ("pos", "n_cig", "cigar")
 DS_FIELDS = tuple(OUT_SCALARS) + tuple(OUT_COLS)
 
 
@@ -66,13 +68,14 @@ class _HostOut:
         self.mem = None
         self.arr = {}
 
-    def ensure(self, n_ss, c_ss, n_ds, c_ds, n_reads):
+    def ensure(self, n_ss, c_ss, n_ds, c_ds, n_reads, ss_fields=SS_FIELDS):
         need = (n_ss, c_ss, n_ds, c_ds, n_reads)
-        if self.cap is not None and all(a >= b for a, b in zip(self.cap, need)):
+        if self.cap is not None and all(a >= b for a, b in zip(self.cap, need)) and \
+                set(self.arr["ss"]) == set(ss_fields):
             return
         cap = tuple(int(max(b, 1) * 1.25) + 64 for b in need)
         specs = []
-        for kind, fields, nrec, ncol in (("ss", SS_FIELDS, cap[0], cap[1]), ("ds", DS_FIELDS, cap[2], cap[3])):
+        for kind, fields, nrec, ncol in (("ss", ss_fields, cap[0], cap[1]), ("ds", DS_FIELDS, cap[2], cap[3])):
             for k in fields:
                 dt = OUT_SCALARS.get(k) or OUT_COLS[k]
                 specs.append((kind, k, np.dtype(dt), nrec if k in OUT_SCALARS else ncol))
@@ -106,6 +109,10 @@ class _HostOut:
 class WMeta(ctypes.Structure):
     _fields_ = [("names", ctypes.c_void_p), ("n_names", ctypes.c_int64), ("fam_code", ctypes.c_void_p),
                 ("fam_rx", ctypes.c_void_p), ("fam_tid", ctypes.c_void_p)]
+
+
+class WMetaSs(ctypes.Structure):
+    _fields_ = [("sub_flag", ctypes.c_void_p), ("sub_mi", ctypes.c_void_p), ("sub_rx", ctypes.c_void_p)]
 
 
 class WRes(ctypes.Structure):
@@ -145,31 +152,49 @@ class _WriterOut:
 class WriterResult:
     """One batch through the device writer: per-family outcomes (0: written),
     duplex lengths, and the BGZF blocks of the records of every family that
-    does not fail."""
+    does not fail.  With the single-strand stream (dcr_submit_write_ss) also
+    ``ss_bgzf`` / ``ss_record_bytes``: the blocks of those families' four
+    single-strand records; None without it."""
 
-    def __init__(self, stream, slot, out, n_fam):
+    def __init__(self, stream, slot, out, n_fam, out_ss=None):
         self._stream, self._slot = stream, slot
         self.fam_fail = out.fam_fail[:n_fam]
         self.ds_len = out.ds_len[:2 * n_fam]
         self.bgzf_bytes, self.record_bytes, self.blocks = (int(x) for x in out.totals[:3])
         self.bgzf = out.blocks.array[:self.bgzf_bytes]
+        self.ss_bgzf = self.ss_record_bytes = None
+        if out_ss is not None:
+            self.ss_bgzf_bytes, self.ss_record_bytes, self.ss_blocks = (int(x) for x in out_ss.totals[:3])
+            self.ss_bgzf = out_ss.blocks.array[:self.ss_bgzf_bytes]
 
-    def record_bytes_of(self, n_fam):
-        """Formatted records of families [0, n_fam) (fetched from the device slot)."""
+    def _fetch_records(self, what_off, what_bytes, n_rec):
         lib, ctx = self._stream.lib, self._stream.ctx._ctx
         from . import _lib
         end = np.zeros(1, np.int64)
-        _lib._check(lib.dcr_slot_fetch(ctx, self._slot, 1, 2 * n_fam, 1, end.ctypes.data))
+        _lib._check(lib.dcr_slot_fetch(ctx, self._slot, what_off, n_rec, 1, end.ctypes.data))
         buf = np.zeros(max(int(end[0]), 1), np.uint8)
-        _lib._check(lib.dcr_slot_fetch(ctx, self._slot, 0, 0, int(end[0]), buf.ctypes.data))
+        _lib._check(lib.dcr_slot_fetch(ctx, self._slot, what_bytes, 0, int(end[0]), buf.ctypes.data))
         return buf[:int(end[0])]
+
+    def record_bytes_of(self, n_fam):
+        """Formatted records of families [0, n_fam) (fetched from the device slot)."""
+        return self._fetch_records(1, 0, 2 * n_fam)
+
+    def ss_record_bytes_of(self, n_fam):
+        """Formatted single-strand records of families [0, n_fam)."""
+        return self._fetch_records(4, 3, 4 * n_fam)
 
 
 class DeviceStream:
     """Asynchronous batches on one GPU context (``_lib.Context``).  With
     ``device_writer`` the records are formatted and BGZF-compressed on the
     device (dcr_submit_write); otherwise the kernel outputs come back for the
-    host writer (dcr_submit)."""
+    host writer (dcr_submit).
+
+    ``ss_output`` (set per run, cli.main): the single-strand records are
+    wanted too: host batches carry their metadata, the device writer makes
+    their stream (dcr_submit_write_ss) and the host path downloads their pos,
+    n_cig and cigar."""
 
     def __init__(self, ctx, n_slots=2, owns_ctx=False, device_writer=True, persistent=False):
         """``persistent``: ``close`` only drains the slots (the context and the
@@ -182,6 +207,8 @@ class DeviceStream:
         self.closed = False
         self._spare = {}                 # reads -> [HostBatch] released by earlier runs
         self.device_writer = device_writer
+        self.ss_output = False
+        self.wouts_ss = None
         self.lib = _lib.load()
         self.n_slots = n_slots
         self.outs = [_HostOut(self.lib) for _ in range(n_slots)]
@@ -191,16 +218,17 @@ class DeviceStream:
         self._pins = []
 
     def host_batch(self, reads=1 << 20):
-        spare = self._spare.get(reads)
+        spare = self._spare.get((reads, self.ss_output))
         if spare:
             return spare.pop()
-        return native_io.HostBatch(reads=reads, alloc=pinned_allocator(self.lib, self._pins))
+        return native_io.HostBatch(reads=reads, alloc=pinned_allocator(self.lib, self._pins),
+                                   ss_meta=self.ss_output)
 
     def release(self, batches):
         """Host batches a run is done with, kept for the next run (persistent)."""
         if self.persistent and not self.closed:
             for hb in batches:
-                self._spare.setdefault(hb.reads, []).append(hb)
+                self._spare.setdefault((hb.reads, hb.ss_meta), []).append(hb)
 
     def submit(self, hb):
         slot = self.next_slot
@@ -219,12 +247,27 @@ class DeviceStream:
             m.fam_code, m.fam_rx, m.fam_tid = (hb.a["fam_code"].ctypes.data, hb.a["fam_rx"].ctypes.data,
                                                hb.a["fam_tid"].ctypes.data)
             self._wres = wo.wres()
+            if self.ss_output:
+                if self.wouts_ss is None:
+                    self.wouts_ss = [_WriterOut(self.lib) for _ in range(self.n_slots)]
+                ws = self.wouts_ss[slot]
+                ws.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3))
+                ms = WMetaSs()
+                ms.sub_flag, ms.sub_mi, ms.sub_rx = (hb.a["sub_flag"].ctypes.data, hb.a["sub_mi"].ctypes.data,
+                                                     hb.a["sub_rx"].ctypes.data)
+                self._wres_ss = ws.wres()
+                _lib._check(self.lib.dcr_submit_write_ss(self.ctx._ctx, slot, ctypes.byref(self._b), ctypes.byref(m),
+                                                         ctypes.byref(ms), ctypes.byref(self._wres),
+                                                         ctypes.byref(self._wres_ss)))
+                self.busy[slot] = True
+                return (slot, s.n_fam, True)
             _lib._check(self.lib.dcr_submit_write(self.ctx._ctx, slot, ctypes.byref(self._b), ctypes.byref(m),
                                                   ctypes.byref(self._wres)))
             self.busy[slot] = True
             return (slot, s.n_fam)
         out = self.outs[slot]
-        out.ensure(4 * s.n_fam, s.ss_cols, 2 * s.n_fam, s.ds_cols, s.n_reads)
+        out.ensure(4 * s.n_fam, s.ss_cols, 2 * s.n_fam, s.ds_cols, s.n_reads,
+                   SS_FIELDS_FULL if self.ss_output else SS_FIELDS)
         self._b = hb.batch_struct()
         so, do = out.dcr_out("ss"), out.dcr_out("ds")
         from . import _lib
@@ -236,20 +279,27 @@ class DeviceStream:
     def result(self, handle):
         from . import _lib
         if self.device_writer:
-            slot, n_fam = handle
+            slot, n_fam = handle[:2]
             wo = self.wouts[slot]
+            ws = self.wouts_ss[slot] if len(handle) > 2 else None
             r = wo.wres()
-            rc = self.lib.dcr_wait_write(self.ctx._ctx, slot, ctypes.byref(r))
-            self.busy[slot] = False
-            if rc == 3 and int(wo.totals[0]) > wo.cap_b:      # DCR_ECAPACITY: grow, fetch again
-                n = int(wo.totals[0])
-                tot = wo.totals[:3].copy()
-                wo.ensure(n_fam, n)
-                wo.totals[:3] = tot
-                _lib._check(self.lib.dcr_slot_fetch(self.ctx._ctx, slot, 2, 0, n, wo.blocks.ptr))
+            if ws is not None:
+                rc = self.lib.dcr_wait_write_ss(self.ctx._ctx, slot, ctypes.byref(r), ctypes.byref(ws.wres()))
             else:
+                rc = self.lib.dcr_wait_write(self.ctx._ctx, slot, ctypes.byref(r))
+            self.busy[slot] = False
+            grown = False
+            for o, what in ((wo, 2), (ws, 5)):
+                if rc == 3 and o is not None and int(o.totals[0]) > o.cap_b:   # DCR_ECAPACITY: grow, fetch again
+                    n = int(o.totals[0])
+                    tot = o.totals[:3].copy()
+                    o.ensure(n_fam, n)
+                    o.totals[:3] = tot
+                    _lib._check(self.lib.dcr_slot_fetch(self.ctx._ctx, slot, what, 0, n, o.blocks.ptr))
+                    grown = True
+            if not grown:
                 _lib._check(rc)
-            return WriterResult(self, slot, wo, n_fam)
+            return WriterResult(self, slot, wo, n_fam, ws)
         slot = handle
         _lib._check(self.lib.dcr_wait(self.ctx._ctx, slot))
         self.busy[slot] = False
@@ -276,7 +326,7 @@ class DeviceStream:
         for o in self.outs:
             if o.mem is not None:
                 o.mem.free()
-        for w in self.wouts:
+        for w in self.wouts + (self.wouts_ss or []):
             for m in (w.small, w.blocks):
                 if m is not None:
                     m.free()
@@ -289,11 +339,12 @@ class CallBackend:
 
     def __init__(self, fn, params):
         self.fn, self.params = fn, params
+        self.ss_output = False
         self._res = {}
         self._k = 0
 
     def host_batch(self, reads=1 << 20):
-        return native_io.HostBatch(reads=reads)
+        return native_io.HostBatch(reads=reads, ss_meta=self.ss_output)
 
     def submit(self, hb):
         ss, ds, info = self.fn(hb.packed(), self.params)

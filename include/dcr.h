@@ -221,6 +221,26 @@ int dcr_submit_write(dcr_ctx *ctx, int slot, const dcr_batch *host_in, const dcr
 int dcr_wait_write(dcr_ctx *ctx, int slot, dcr_wres *res);
 int dcr_slot_fetch(dcr_ctx *ctx, int slot, int what, int64_t off, int64_t n, void *dst);
 
+/* The single-strand consensus reads as a second stream.  dcr_submit_write_ss
+ * is dcr_submit_write and, for every family that does not fail, the four
+ * records make_consensus_read(method="single_strand") returns (:1352-1384;
+ * order A1 B2 B1 A2; name get_consensus_id :909-920, flag of the subfamily's
+ * first read :957-958, tags MI RX sQ sd sD sM se sE add_tags :1054-1073, no
+ * mate fields), formatted as libdcr_io's dcr_fmt_write_ss formats them and
+ * BGZF-compressed on their own.  res_ss: bgzf, cap_bgzf and totals are used.
+ * dcr_wait_write_ss fills both results; on DCR_ECAPACITY the totals[0] of the
+ * two tell which stream's blocks to fetch again.  dcr_slot_fetch: what 3 =
+ * single-strand record bytes, 4 = their int64 record offsets [4F+1], 5 =
+ * their BGZF blocks. */
+typedef struct dcr_wmeta_ss {
+    const uint16_t *sub_flag;    /* [4F] flag of each subfamily's first read       */
+    const int64_t *sub_mi;       /* [4F] offsets in dcr_wmeta.names of its whole MI */
+    const int64_t *sub_rx;       /* [4F] offsets of its RX                          */
+} dcr_wmeta_ss;
+int dcr_submit_write_ss(dcr_ctx *ctx, int slot, const dcr_batch *host_in, const dcr_wmeta *meta,
+                        const dcr_wmeta_ss *meta_ss, dcr_wres *res, dcr_wres *res_ss);
+int dcr_wait_write_ss(dcr_ctx *ctx, int slot, dcr_wres *res, dcr_wres *res_ss);
+
 /* CPU restatement with the same contract (oracle/, test infrastructure):
    host pointers, single thread (or n_threads > 1) */
 int dcr_oracle_run(const dcr_params *params, const dcr_batch *in, dcr_out *ss, dcr_out *ds,

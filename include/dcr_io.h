@@ -78,6 +78,9 @@ typedef struct dcr_ingest_cfg {
  * hook is set (dcr_io_set_inflate_hook), e.g. a count-only pass running
  * beside a GPU pass */
 #define DCR_INGEST_HOST_INFLATE 1
+/* fill dcr_host_batch.sub_flag / sub_mi / sub_rx (the single-strand records'
+ * metadata) where those pointers are not NULL */
+#define DCR_INGEST_SS_META 2
 
 /* One host batch.  The caller allocates every array (pinned memory for the
  * GPU path) and sets the capacities; dcr_ingest_next fills it.  The first
@@ -122,6 +125,12 @@ typedef struct dcr_host_batch {
     char *names;            /* NUL-terminated strings                        */
     uint8_t *side_exc;      /* raw BAM records (block_size + body) for _filteredreads.bam    */
     uint8_t *side_filt;     /* raw BAM records for _filteredfamilies.bam                     */
+    /* per subfamily: the first packed read (list_of_reads[0] of its
+     * make_consensus_read call; the sample's first read after downsampling).
+     * Optional: NULL, or filled under DCR_INGEST_SS_META */
+    uint16_t *sub_flag;     /* [4*cap_fam] its flag (get_consensus_flag :957-958)            */
+    int64_t *sub_mi;        /* [4*cap_fam] names offset of its whole MI value (:1057)        */
+    int64_t *sub_rx;        /* [4*cap_fam] names offset of its RX value                      */
     /* filled by dcr_ingest_next */
     int32_t n_fam, n_reads;
     int64_t n_cigar, n_bases, ss_cols, ds_cols;
@@ -214,8 +223,8 @@ int dcr_bgzw_sizes(dcr_bgzw *w, int64_t *out2);
 
 /* ---- consensus records ----
  * Host copies of the kernel outputs the records need (include/dcr.h
- * dcr_out): single-strand status, mapq, len, n_de, D, M, E, seq, qual, d, e;
- * duplex: every field.  Regions follow hb->ss_col_off / hb->ds_col_off. */
+ * dcr_out): single-strand status, mapq, len, n_de, D, M, E, seq, qual, d, e
+ * (and pos, n_cig, cigar for dcr_fmt_write_ss); duplex: every field.  Regions follow hb->ss_col_off / hb->ds_col_off. */
 typedef struct dcr_fmt_out {
     const uint8_t *status;
     const int32_t *pos, *mapq, *len, *n_cig, *n_de, *D, *M;
@@ -244,6 +253,11 @@ int32_t dcr_fmt_scan(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_
  * of families that fail must not be in the range) and write them. */
 int dcr_fmt_write(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds,
                   int32_t n_fam);
+/* Format the four single-strand records (A1, B2, B1, A2: make_consensus_read
+ * method="single_strand", tags add_tags :1054-1073, no mate fields) of
+ * processed families [0, n_fam) and write them.  hb carries sub_flag, sub_mi
+ * and sub_rx (DCR_INGEST_SS_META); ss holds every field of dcr_fmt_out. */
+int dcr_fmt_write_ss(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, int32_t n_fam);
 
 /* ---- the GPU BGZF block compressor (csrc/dcr_deflate.h) emulated lane by
  * lane on the host, for tests: one BGZF block of in[0, n) (n <= 0xff00) into
