@@ -46,6 +46,8 @@ EXPORTS = {
     "dcr_wait_write_ss": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "dcr_slot_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                       ctypes.c_void_p]),
+    "dcr_set_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "dcr_slot_filter_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     # include/dcr_inflate.h: BGZF inflate on the device
     "dcr_inflater_create": (ctypes.c_void_p, [ctypes.c_int]),
     "dcr_inflater_destroy": (None, [ctypes.c_void_p]),
@@ -120,6 +122,7 @@ class Context:
         if not self._ctx:
             raise DcrError(f"dcr_create failed: {lib.dcr_last_error().decode()}")
         self.want_info = want_info
+        self.filter = None
         if want_info:
             _check(lib.dcr_set_options(self._ctx, 1))
 
@@ -138,6 +141,15 @@ class Context:
         self.params = params
         self._p = build_dcr_params(params)
         _check(load().dcr_set_params(self._ctx, ctypes.byref(self._p)))
+
+    def set_filter(self, flt):
+        """``flt``: a params.ConsensusFilter for the batches the device writer
+        takes from now on, or None (off: dcr_set_filter)."""
+        if flt == self.filter:
+            return
+        s = flt.as_struct() if flt is not None else None
+        _check(load().dcr_set_filter(self._ctx, ctypes.byref(s) if s is not None else None))
+        self.filter = flt
 
     @property
     def stream(self):

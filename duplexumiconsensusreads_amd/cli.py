@@ -18,6 +18,11 @@ The per-record work runs natively (libdcr_io.so, include/dcr_io.h):
 single-strand consensus reads of every written family, which the reference
 builds (``make_consensus_read(method="single_strand")`` :1564-1569) and drops.
 
+``--filter_*`` (not reference flags either) mask weak duplex bases and drop
+families whose duplex records have too little support or too many
+disagreements (include/dcr.h ``dcr_filter``): the step that otherwise follows
+on the written file.  Off by default; without one nothing changes.
+
 Batches are pipelined: a thread ingests batch k+1 while the device runs batch
 k and the main thread writes batch k-1.
 
@@ -47,7 +52,8 @@ from typing import Optional
 import numpy as np
 
 from . import native_io
-from .params import ConsensusParams
+from . import params as params_mod
+from .params import ConsensusFilter, ConsensusParams
 
 SPLIT_NAMES = {0: "A1", 1: "B2", 2: "B1", 3: "A2"}      # split_dict (:1511)
 EQX_LINE = 'Symbols "x" and "=" were found in CIGAR strings and were changed to "M"'   # :375
@@ -86,6 +92,21 @@ def parse_args(argv):
     # written family (make_consensus_read method="single_strand", which the
     # reference builds and drops) into a BAM of their own
     ap.add_argument("--single_strand_output", required=False, default=None, type=str)
+    # not reference flags: the consensus filters (include/dcr.h dcr_filter); any one turns them on
+    ap.add_argument("--filter_min_base_quality", required=False, default=None, metavar="Q",
+                    type=params_mod.filter_min_base_quality,
+                    help="mask duplex bases below Q: 'N' with quality min(q, 2)")
+    ap.add_argument("--filter_min_reads", required=False, default=None, metavar="T[,A[,B]]",
+                    type=params_mod.filter_min_reads,
+                    help="keep a duplex read with aD + bD >= T, max(aD, bD) >= A, min(aD, bD) >= B")
+    ap.add_argument("--filter_max_read_error_rate", required=False, default=None, metavar="C[,S]",
+                    type=params_mod.filter_max_read_error_rate, help="keep a duplex read with cE <= C, aE and bE <= S")
+    ap.add_argument("--filter_max_no_call_fraction", required=False, default=None, metavar="X",
+                    type=params_mod.filter_max_no_call_fraction,
+                    help="keep a duplex read with at most X of its bases 'N' after masking")
+    ap.add_argument("--filter_min_mean_base_quality", required=False, default=None, metavar="Q",
+                    type=params_mod.filter_min_mean_base_quality,
+                    help="keep a duplex read whose mean base quality after masking is at least Q")
     return ap.parse_args(argv)
 
 
@@ -228,10 +249,11 @@ def gpu_inflate(device: int = 0):
     return got[0]
 
 
-def _as_backend(backend, params, device=0, ss_output=False):
+def _as_backend(backend, params, device=0, ss_output=False, flt=None):
     """``ss_output``: this run also writes the single-strand records (a
     property of the run, set on the backend each time: the default backend
-    is kept across runs)."""
+    is kept across runs).  ``flt``: this run's ConsensusFilter or None,
+    set each time in the same way."""
     if backend is None:
         be = default_backend(params, device)
     elif hasattr(backend, "submit"):
@@ -243,6 +265,10 @@ def _as_backend(backend, params, device=0, ss_output=False):
         be.ss_output = ss_output
     elif ss_output:
         raise ValueError("this backend cannot produce the single-strand records")
+    if hasattr(be, "filter"):
+        be.filter = flt
+    elif flt is not None:
+        raise ValueError("this backend cannot apply the consensus filters")
     return be
 
 
@@ -274,11 +300,17 @@ class _Driver:
         self.args, self.params, self.backend = args, params, backend
         self.ing, self.cons, self.excl, self.unproc, self.sscs = ing, cons, excl, unproc, sscs
         self.verbose = args.verbose
+        self.filter = ConsensusFilter.from_args(args)
+        # families dropped by the filter, per reason, and bases masked in the written ones (the summary's counters)
+        self.filter_counts = {} if self.filter is None else dict(
+            {"filter_dropped": 0, "filter_masked": 0}, **{"filter_" + name: 0 for _, name in params_mod.FILT_REASONS})
         # per-stage busy seconds and totals (bench.py --e2e reports them)
         self.trace = None          # optional [(stage, t0, t1)] (bench.py)
         self.ends_at_eof = True    # False for a sharded range that stops before the end
         self.stats = {"batches": 0, "consensus_records": 0, "consensus_bases": 0, "ingest_s": 0.0,
                       "submit_s": 0.0, "wait_s": 0.0, "write_s": 0.0, "idle_s": 0.0}
+        if self.filter is not None:
+            self.stats.update(filter_dropped_families=0, filter_masked_bases=0)
 
     # -- stdout of one batch, in the reference's order --------------------------
     def _prints(self, hb, fail_f, kind, which, last_batch):
@@ -418,18 +450,33 @@ class _Driver:
                 elif fail_f:
                     self.sscs.write(res.ss_record_bytes_of(fail_f))
             lens = res.ds_len[:2 * fail_f]
+            filt = res.fam_filt[:fail_f] if self.filter is not None else None
         else:
             ss, ds, rstat = res
             fail_f, kind, which = native_io.first_failure(hb, ss, ds, F, rstat)
             self._prints(hb, fail_f, kind, which, last_batch)
-            self.cons.write_consensus(hb, ss, ds, fail_f)
+            filt = native_io.apply_filter(hb, ss, ds, self.filter, fail_f) if self.filter is not None else None
+            self.cons.write_consensus(hb, ss, ds, fail_f, filt)
             if self.sscs is not None:
-                self.sscs.write_consensus_ss(hb, ss, fail_f)
+                self.sscs.write_consensus_ss(hb, ss, fail_f, filt)
             lens = np.ctypeslib.as_array(ctypes.cast(ds.len, ctypes.POINTER(ctypes.c_int32)), (2 * F,))[:2 * fail_f] \
                 if F else np.zeros(0, np.int32)
         st["batches"] += 1
-        st["consensus_records"] += 2 * fail_f
-        st["consensus_bases"] += int(lens.sum())
+        if filt is None:
+            st["consensus_records"] += 2 * fail_f
+            st["consensus_bases"] += int(lens.sum())
+        else:
+            # written records only; the families before a failure are filtered as any other
+            why = filt & 0xff
+            kept = why == 0
+            st["consensus_records"] += 2 * int(kept.sum())
+            st["consensus_bases"] += int(lens.reshape(-1, 2)[kept].sum())
+            fc = self.filter_counts
+            fc["filter_dropped"] += int((~kept).sum())
+            fc["filter_masked"] += int((filt[kept] >> 8).sum())
+            for bit, name in params_mod.FILT_REASONS:
+                fc["filter_" + name] += int(((why & bit) != 0).sum())
+            st["filter_dropped_families"], st["filter_masked_bases"] = fc["filter_dropped"], fc["filter_masked"]
         st["wait_s"] += t1 - t0
         if fail_f < F:
             t = int(np.nonzero(hb.a["tab_proc"][:hb.s.n_tab] == fail_f)[0][0])
@@ -589,7 +636,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
         raise ReferenceExit(1)
     _check_ss_output(args)
     ss_path = args.single_strand_output
-    be = _as_backend(backend, params, args.device, ss_path is not None)
+    be = _as_backend(backend, params, args.device, ss_path is not None, ConsensusFilter.from_args(args))
     cons, excl, unproc, *rest = _open_writers(
         [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
          "%s_filteredfamilies.bam" % consensus_filename[:-4]] + ([ss_path] if ss_path else []), ing.header, args, ing)
@@ -610,6 +657,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
         c = ing.counters()
         if stats is not None:
             stats.update(c)
+        c.update(drv.filter_counts)
         if args.verbose:
             print("\n Input file has been completely read \n")
         _print_summary(c)
@@ -667,6 +715,14 @@ def _print_summary(c):
           (processed, processed / tot_f * 100))
     print("\n A total of %d families (%.2f %%) were filtered out due to not enough reads to generate a "
           "consensus read." % (excluded, excluded / tot_f * 100))
+    if "filter_dropped" in c:
+        # only with a --filter_* option: of the processed families
+        dropped = c["filter_dropped"]
+        print("\n A total of %d families (%.2f %%) were removed by the consensus filters."
+              % (dropped, dropped / max(processed, 1) * 100))
+        print("\n Families removed per rule: " + ", ".join("%s %d" % (name, c["filter_" + name])
+                                                            for _, name in params_mod.FILT_REASONS))
+        print("\n A total of %d bases were masked in the consensus reads that were written." % c["filter_masked"])
 
 
 # -- sharded mode: one process per GPU over ranges of whole families ---------------
@@ -770,7 +826,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
     ing = native_io.Ingest(path, params.min_map_quality, params.min_reads, params.max_reads,
                            params.min_base_quality, args.threads, rng_range[0], rng_range[1],
                            ss_meta=len(parts) > 3)
-    be = _as_backend(backend, params, device, len(parts) > 3)
+    be = _as_backend(backend, params, device, len(parts) > 3, ConsensusFilter.from_args(args))
     cons, excl, unproc, *rest = _open_writers(parts, header, args, ing)
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng_state)
@@ -789,7 +845,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
         res["status"], res["exc_args"] = "error", (repr(e),)
     finally:
         res["calls"] = ing.sample_calls()
-        res["counters"] = ing.counters()
+        res["counters"] = dict(ing.counters(), **drv.filter_counts)
         res["stats"] = dict(drv.stats)
         res["stdout"] = out.getvalue()
         try:

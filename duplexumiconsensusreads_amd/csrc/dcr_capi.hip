@@ -217,6 +217,7 @@ struct WriterBufs {
     uint8_t *comp;
     int64_t *tot;
     uint32_t *tok;
+    int32_t *fam_filt;      // k_filter's outcomes; null unless a filter is set (dcr_set_filter)
 };
 
 // The second stream of dcr_submit_write_ss: the single-strand records'
@@ -238,8 +239,9 @@ struct WriterSsBufs {
 // F families, n_names bytes of names, a record stream of at most B bytes in
 // at most nbm blocks, gd k_deflate workgroups; with ws, the single-strand
 // stream's regions after them (the first stream's layout does not change)
+// and with filt, k_filter's outcomes (no region without it)
 void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w,
-                 WriterSsBufs *ws = nullptr) {
+                 WriterSsBufs *ws = nullptr, bool filt = false) {
     w.names = p.take<char>((size_t)n_names + 1);
     w.fam_code = p.take<int64_t>((size_t)F);
     w.fam_rx = p.take<int64_t>(2 * (size_t)F);
@@ -256,6 +258,7 @@ void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd
     w.comp = p.take<uint8_t>((size_t)nbm * dfl::kSlot);
     w.tot = p.take<int64_t>(4);
     w.tok = p.take<uint32_t>((size_t)gd * dfl::kTokWords);
+    w.fam_filt = filt ? p.take<int32_t>((size_t)F) : nullptr;
     if (!ws) return;
     ws->sub_flag = p.take<uint16_t>(4 * (size_t)F);
     ws->sub_mi = p.take<int64_t>(4 * (size_t)F);
@@ -313,6 +316,7 @@ struct dcr_ctx {
         bool writer = false, writer_ss = false;
         hipEvent_t ev_h2d = nullptr, ev_comp = nullptr, ev_d2h = nullptr;
         int *h_err = nullptr;     // pinned copy of the batch's capacity flag
+        int32_t *h_fam_filt = nullptr;   // the caller's pinned fam_filt (dcr_slot_filter_out), or null
         bool busy = false;
     } slots[DCR_MAX_SLOTS];
     dcr::Workspace w{};
@@ -322,6 +326,7 @@ struct dcr_ctx {
     int options = 0;    // DCR_OPT_*
     int wide_ok = 0;    // the general kernel's decision pass may run (wide_table)
     dcr_params host_params{};
+    dcr_filter filter{};    // dcr_set_filter; active == 0: off
     // fast-kernel constants (fast_constants)
     uint32_t fast_kq = 0, fast_kqlo = 0;
     int fast_maxq = 0, fast_t16 = 0, fast_r_safe = 0, fast_qlo = 0;
@@ -997,11 +1002,14 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         wsb.nbm = wsb.B / (int64_t)dfl::kMaxIn + 2;
         wsb.gd = (unsigned)std::max<int64_t>(1, std::min<int64_t>(wsb.nbm, (int64_t)c->n_cu * c->dfl_blocks));
     }
+    const bool filt = c->filter.active != 0;
+    if (filt && F && !S.h_fam_filt)
+        return fail(DCR_EARG, "a filter is set but the slot has no fam_filt destination (dcr_slot_filter_out)");
     Plan wsz;
-    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr);
+    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt);
     if (wsz.off > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wsz.off + wsz.off / 8));
     Plan wp{(char *)S.wbuf.p};
-    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr);
+    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt);
     // H2D: inputs and writer metadata on the copy stream
     HIP_TRY(upload_inputs(h, db, c->s_h2d));
     if (m->n_names) HIP_TRY(hipMemcpyAsync(wb.names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
@@ -1035,10 +1043,17 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     A.rec_size = wb.rec_size;
     A.rec_off = wb.rec_off;
     A.stream = wb.stream;
+    A.fam_filt = wb.fam_filt;
     HIP_TRY(hipMemsetAsync(wb.rec_size, 0, 8 * (size_t)(2 * F + 1), c->stream));
     HIP_TRY(hipMemsetAsync(wb.bsz, 0, 8 * (size_t)(nbm + 2), c->stream));
     if (F) {
         hipLaunchKernelGGL(dcrw::k_famfail, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, c->stream, A);
+        if (filt) {
+            // one wave per family, before anything reads the duplex seq / qual
+            dcrw::FilterArgs Fa{dout[0], dout[1], db.ds_col_off, wb.fam_fail, wb.fam_filt, (int32_t)F, c->filter};
+            const unsigned gf = (unsigned)std::max<int64_t>(1, std::min<int64_t>((F + 3) / 4, (int64_t)c->n_cu * 8));
+            hipLaunchKernelGGL(dcrw::k_filter, dim3(gf), dim3(256), 0, c->stream, Fa);
+        }
         const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((2 * F + 3) / 4, (int64_t)c->n_cu * 8));
         hipLaunchKernelGGL(dcrw::k_fmt_size, dim3(g), dim3(256), 0, c->stream, A);
         HIP_TRY(hipGetLastError());
@@ -1072,6 +1087,7 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         As.sub_rx = wsb.sub_rx;
         As.n_fam = (int32_t)F;
         As.fam_fail = wb.fam_fail;
+        As.fam_filt = wb.fam_filt;
         As.rec_size = wsb.rec_size;
         As.rec_off = wsb.rec_off;
         As.stream = wsb.stream;
@@ -1102,6 +1118,7 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     if (F) {
         HIP_TRY(hipMemcpyAsync(res->fam_fail, wb.fam_fail, 4 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
         HIP_TRY(hipMemcpyAsync(res->ds_len, wb.ds_len, 8 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
+        if (filt) HIP_TRY(hipMemcpyAsync(S.h_fam_filt, wb.fam_filt, 4 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
     }
     HIP_TRY(hipMemcpyAsync(res->totals, wb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
     if (ms) HIP_TRY(hipMemcpyAsync(res_ss->totals, wsb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
@@ -1116,6 +1133,35 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     S.writer = true;
     S.writer_ss = ms != nullptr;
     S.busy = true;
+    return DCR_OK;
+}
+
+int dcr_set_filter(dcr_ctx *c, const dcr_filter *f) {
+    if (!c) return fail(DCR_EARG, "NULL context");
+    if (!f || f->active == 0) {
+        c->filter = dcr_filter{};
+        return DCR_OK;
+    }
+    const int all = DCR_FILT_MIN_READS | DCR_FILT_ERROR_RATE | DCR_FILT_NO_CALL | DCR_FILT_MEAN_QUAL | DCR_FILT_MASK_BASES;
+    if (f->active & ~all) return fail(DCR_EARG, "unknown filter bits");
+    if ((f->active & DCR_FILT_MASK_BASES) && f->min_base_quality < 0) return fail(DCR_EARG, "filter min_base_quality < 0");
+    if ((f->active & DCR_FILT_MIN_READS) && !(f->min_reads[0] >= f->min_reads[1] && f->min_reads[1] >= f->min_reads[2]))
+        return fail(DCR_EARG, "filter min_reads must be total >= larger strand >= smaller strand");
+    auto unit = [](double x) { return x >= 0.0 && x <= 1.0; };
+    if ((f->active & DCR_FILT_ERROR_RATE) && !(unit(f->max_error_rate[0]) && unit(f->max_error_rate[1])))
+        return fail(DCR_EARG, "filter max_error_rate outside [0, 1]");
+    if ((f->active & DCR_FILT_NO_CALL) && !unit(f->max_no_call_fraction))
+        return fail(DCR_EARG, "filter max_no_call_fraction outside [0, 1]");
+    if ((f->active & DCR_FILT_MEAN_QUAL) && !(f->min_mean_base_quality >= 0.0))
+        return fail(DCR_EARG, "filter min_mean_base_quality < 0");
+    c->filter = *f;
+    return DCR_OK;
+}
+
+int dcr_slot_filter_out(dcr_ctx *c, int slot, int32_t *fam_filt) {
+    if (!c || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
+    if (c->slots[slot].busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
+    c->slots[slot].h_fam_filt = fam_filt;
     return DCR_OK;
 }
 

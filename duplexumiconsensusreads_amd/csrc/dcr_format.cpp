@@ -559,12 +559,13 @@ int32_t dcr_fmt_scan(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_
     return n_fam;
 }
 
-int dcr_fmt_write(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds,
-                  int32_t n_fam) {
+int dcr_fmt_write_filt(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds,
+                       int32_t n_fam, const int32_t *fam_filt) {
     if (!w || !hb || !ss || !ds || n_fam < 0 || n_fam > hb->n_fam) return fail(DCR_IO_EARG, "bad arguments");
     if (w->bad) return fail(DCR_IO_EFILE, "writer failed earlier");
     const Ctx c{hb, ss, ds};
     return write_chunked(w, hb, n_fam, [&](int32_t f, const char *code, size_t lc, Buf &o) {
+        if (fam_filt && (fam_filt[f] & 0xff)) return;
         for (int j = 0; j < 2; ++j) {
             o.reserve(record_bound(c, f, j, lc));
             format_record(c, f, j, code, lc, o);
@@ -572,7 +573,13 @@ int dcr_fmt_write(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, 
     });
 }
 
-int dcr_fmt_write_ss(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, int32_t n_fam) {
+int dcr_fmt_write(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds,
+                  int32_t n_fam) {
+    return dcr_fmt_write_filt(w, hb, ss, ds, n_fam, nullptr);
+}
+
+int dcr_fmt_write_ss_filt(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, int32_t n_fam,
+                          const int32_t *fam_filt) {
     if (!w || !hb || !ss || n_fam < 0 || n_fam > hb->n_fam) return fail(DCR_IO_EARG, "bad arguments");
     if (!hb->sub_flag || !hb->sub_mi || !hb->sub_rx)
         return fail(DCR_IO_EARG, "the batch carries no single-strand metadata (DCR_INGEST_SS_META)");
@@ -580,11 +587,60 @@ int dcr_fmt_write_ss(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *s
     if (w->bad) return fail(DCR_IO_EFILE, "writer failed earlier");
     const Ctx c{hb, ss, nullptr};
     return write_chunked(w, hb, n_fam, [&](int32_t f, const char *code, size_t lc, Buf &o) {
+        if (fam_filt && (fam_filt[f] & 0xff)) return;
         for (int k = 0; k < 4; ++k) {
             o.reserve(record_bound_ss(c, f, k, lc));
             format_record_ss(c, f, k, code, lc, o);
         }
     });
+}
+
+int dcr_fmt_write_ss(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, int32_t n_fam) {
+    return dcr_fmt_write_ss_filt(w, hb, ss, n_fam, nullptr);
+}
+
+// the rules of include/dcr.h (dcr_filter), as dcr_writer.hip's k_filter applies them
+int dcr_fmt_filter(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds, const dcr_filter *T,
+                   int32_t n_fam, int32_t *fam_filt) {
+    if (!hb || !ss || !ds || !T || !fam_filt || n_fam < 0 || n_fam > hb->n_fam) return fail(DCR_IO_EARG, "bad arguments");
+    const uint32_t minq =
+        (T->active & DCR_FILT_MASK_BASES) ? (uint32_t)(T->min_base_quality < 256 ? T->min_base_quality : 256) : 0u;
+    for (int32_t f = 0; f < n_fam; ++f) {
+        uint32_t why = 0, masked = 0;
+        for (int j = 0; j < 2; ++j) {
+            const int32_t k = 2 * f + j, a = 4 * f + 2 * j, b = a + 1;
+            const int64_t ro = hb->ds_col_off[k];
+            const int64_t L = ds->len[k];
+            uint8_t *sq = const_cast<uint8_t *>(ds->seq) + ro, *ql = const_cast<uint8_t *>(ds->qual) + ro;
+            uint32_t n_n = 0, q_sum = 0;
+            for (int64_t i = 0; i < L; ++i) {
+                if (ql[i] < minq) {
+                    sq[i] = 'N';
+                    if (ql[i] > 2) ql[i] = 2;
+                    ++masked;
+                }
+                n_n += sq[i] == 'N';
+                q_sum += ql[i];
+            }
+            const int32_t aD = ss->D[a], bD = ss->D[b];
+            if (T->active & DCR_FILT_MIN_READS) {
+                const int32_t hi = aD > bD ? aD : bD, lo = aD > bD ? bD : aD;
+                if (!((int64_t)aD + bD >= T->min_reads[0] && hi >= T->min_reads[1] && lo >= T->min_reads[2]))
+                    why |= DCR_FILT_MIN_READS;
+            }
+            if (T->active & DCR_FILT_ERROR_RATE)
+                if (!(ds->E[k] <= T->max_error_rate[0] && ss->E[a] <= T->max_error_rate[1] &&
+                      ss->E[b] <= T->max_error_rate[1]))
+                    why |= DCR_FILT_ERROR_RATE;
+            // one double multiply each (built with -ffp-contract=off)
+            if ((T->active & DCR_FILT_NO_CALL) && (double)n_n > T->max_no_call_fraction * (double)L)
+                why |= DCR_FILT_NO_CALL;
+            if ((T->active & DCR_FILT_MEAN_QUAL) && (double)q_sum < T->min_mean_base_quality * (double)L)
+                why |= DCR_FILT_MEAN_QUAL;
+        }
+        fam_filt[f] = (int32_t)(why | (masked << 8));
+    }
+    return DCR_IO_OK;
 }
 
 }  // extern "C"

@@ -23,6 +23,17 @@ struct FmtArgs {
     int64_t *rec_size;              // [2F+1] (the last one 0: the scan's total)
     int64_t *rec_off;               // [2F+1]
     uint8_t *stream;                // formatted records
+    const int32_t *fam_filt;        // [F] from k_filter, or null (no filter set): low byte set = dropped
+};
+
+// the consensus filters (k_filter, dcr_set_filter)
+struct FilterArgs {
+    dcr_out ss, ds;                 // device kernel outputs; ds.seq / ds.qual are masked in place
+    const int64_t *ds_col_off;      // [2F+1]
+    const int32_t *fam_fail;        // [F] from k_famfail
+    int32_t *fam_filt;              // [F] reason bits | masked bases << 8
+    int32_t n_fam;
+    dcr_filter flt;
 };
 
 // the single-strand records' writer (k_fmt_size_ss / k_fmt_write_ss)
@@ -38,6 +49,7 @@ struct FmtSsArgs {
     const int64_t *sub_mi, *sub_rx; // [4F] names offsets of read0's MI / RX
     int32_t n_fam;
     const int32_t *fam_fail;        // [F] from k_famfail
+    const int32_t *fam_filt;        // [F] from k_filter, or null
     int64_t *rec_size;              // [4F+1] (the last one 0: the scan's total)
     int64_t *rec_off;               // [4F+1]
     uint8_t *stream;                // formatted records
@@ -63,6 +75,7 @@ struct CompactArgs {
 };
 
 __global__ void k_famfail(FmtArgs A);
+__global__ void k_filter(FilterArgs A);
 __global__ void k_fmt_size(FmtArgs A);
 __global__ void k_fmt_write(FmtArgs A);
 __global__ void k_fmt_size_ss(FmtSsArgs A);

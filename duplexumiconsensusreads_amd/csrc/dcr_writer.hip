@@ -3,7 +3,9 @@
 // HBM, the failure scan, and the BGZF compression of the record stream
 // (dcr_deflate.h), so that only compressed blocks cross PCIe.  On request
 // (dcr_submit_write_ss) also the four single-strand records of every family,
-// as a second record stream compressed by the same kernels.
+// as a second record stream compressed by the same kernels; and with a filter
+// set (dcr_set_filter) k_filter first, which masks weak duplex bases and marks
+// the families neither stream writes.
 //
 // Reference (/root/reference/DuplexUMIConsensusReads.py): record fields
 // make_consensus_read :1352-1384, names / flags :892-968, duplex tags
@@ -271,13 +273,84 @@ __device__ void rec_write(const FmtArgs &A, const Rec &r, uint8_t *o, uint32_t t
     w.b1(0);
 }
 
-// one wave per duplex record; records of failing families get size 0
+// ---- the consensus filters (dcr_set_filter; include/dcr.h states the rules).
+// One wave per family, both duplex records.  The lanes stride the record's
+// seq / qual region a dword (four bases) at a time: regions start on
+// 16-column boundaries and are whole multiples of 16 columns, so the last
+// partial word stays inside the record's own region; its bytes at or past
+// len are neither counted nor changed.  Bases below min_base_quality are
+// masked in place, then 'N' bases, the quality sum and the masked bases are
+// wave-reduced and lane 0 tests the rules on the record's scalars.
+__global__ __launch_bounds__(256) void k_filter(FilterArgs A) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;
+    const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
+    const dcr_filter &T = A.flt;
+    // quality bytes are below 256: a larger threshold masks every base
+    const uint32_t minq = (T.active & DCR_FILT_MASK_BASES) ? (uint32_t)(T.min_base_quality < 256 ? T.min_base_quality : 256) : 0u;
+    for (int64_t f = wave; f < A.n_fam; f += nw) {
+        if (A.fam_fail[f] != 0) {
+            if (lane_id() == 0) A.fam_filt[f] = 0;
+            continue;
+        }
+        uint32_t why = 0, masked = 0;
+        for (int j = 0; j < 2; ++j) {
+            const int64_t k = 2 * f + j, a = 4 * f + 2 * j, b = a + 1;
+            const int64_t ro = A.ds_col_off[k], room = A.ds_col_off[k + 1] - ro;
+            int64_t L = A.ds.len[k];
+            L = L < 0 ? 0 : L > room ? room : L;
+            uint32_t *sq = reinterpret_cast<uint32_t *>(A.ds.seq + ro);
+            uint32_t *ql = reinterpret_cast<uint32_t *>(A.ds.qual + ro);
+            uint32_t n_n = 0, q_sum = 0, n_m = 0;
+            for (int64_t w = lane_id(); 4 * w < L; w += kW) {
+                const uint32_t s0 = sq[w], q0 = ql[w];
+                const int nb = L - 4 * w < 4 ? (int)(L - 4 * w) : 4;
+                uint32_t s1 = s0, q1 = q0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (i >= nb) break;
+                    uint32_t sb = (s0 >> (8 * i)) & 0xffu, qb = (q0 >> (8 * i)) & 0xffu;
+                    if (qb < minq) {
+                        sb = 'N';
+                        qb = qb < 2 ? qb : 2;
+                        s1 = (s1 & ~(0xffu << (8 * i))) | (sb << (8 * i));
+                        q1 = (q1 & ~(0xffu << (8 * i))) | (qb << (8 * i));
+                        ++n_m;
+                    }
+                    n_n += sb == 'N';
+                    q_sum += qb;
+                }
+                if (s1 != s0) sq[w] = s1;
+                if (q1 != q0) ql[w] = q1;
+            }
+            n_n = wave_sum(n_n);
+            q_sum = wave_sum(q_sum);
+            masked += wave_sum(n_m);
+            const int32_t aD = A.ss.D[a], bD = A.ss.D[b];
+            if (T.active & DCR_FILT_MIN_READS) {
+                const int32_t hi = aD > bD ? aD : bD, lo = aD > bD ? bD : aD;
+                if (!((int64_t)aD + bD >= T.min_reads[0] && hi >= T.min_reads[1] && lo >= T.min_reads[2]))
+                    why |= DCR_FILT_MIN_READS;
+            }
+            if (T.active & DCR_FILT_ERROR_RATE)
+                if (!(A.ds.E[k] <= T.max_error_rate[0] && A.ss.E[a] <= T.max_error_rate[1] &&
+                      A.ss.E[b] <= T.max_error_rate[1]))
+                    why |= DCR_FILT_ERROR_RATE;
+            if ((T.active & DCR_FILT_NO_CALL) && (double)n_n > T.max_no_call_fraction * (double)L)
+                why |= DCR_FILT_NO_CALL;
+            if ((T.active & DCR_FILT_MEAN_QUAL) && (double)q_sum < T.min_mean_base_quality * (double)L)
+                why |= DCR_FILT_MEAN_QUAL;
+        }
+        if (lane_id() == 0) A.fam_filt[f] = (int32_t)(why | (masked << 8));
+    }
+}
+
+// one wave per duplex record; records of failing or dropped families get size 0
 __global__ __launch_bounds__(256) void k_fmt_size(FmtArgs A) {
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;
     const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
     for (int64_t k = wave; k < 2LL * A.n_fam; k += nw) {
         uint32_t n = 0;
-        if (A.fam_fail[k >> 1] == 0) {
+        if (A.fam_fail[k >> 1] == 0 && !(A.fam_filt && (A.fam_filt[k >> 1] & 0xff))) {
             Rec r;
             rec_setup(A, (int32_t)k, r);
             n = rec_size(A, r);
@@ -401,7 +474,7 @@ __global__ __launch_bounds__(256) void k_fmt_size_ss(FmtSsArgs A) {
     const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
     for (int64_t s = wave; s < 4LL * A.n_fam; s += nw) {
         uint32_t n = 0;
-        if (A.fam_fail[s >> 2] == 0) {
+        if (A.fam_fail[s >> 2] == 0 && !(A.fam_filt && (A.fam_filt[s >> 2] & 0xff))) {
             RecSs r;
             rec_setup_ss(A, (int32_t)s, r);
             n = rec_size_ss(A, r);

@@ -103,6 +103,9 @@ def load():
             "dcr_fmt_scan": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
             "dcr_fmt_write": (_i32, [_vp, _vp, _vp, _vp, _i32]),
             "dcr_fmt_write_ss": (_i32, [_vp, _vp, _vp, _i32]),
+            "dcr_fmt_filter": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
+            "dcr_fmt_write_filt": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
+            "dcr_fmt_write_ss_filt": (_i32, [_vp, _vp, _vp, _i32, _vp]),
             "dcr_synth_write": (_i32, [_vp, _vp, _i32]),
             "dcr_deflate_emulate": (_i64, [_vp, _i64, _vp]),
             "dcr_deflate_lengths_ab": (_i32, [_vp, _i32, _vp, _vp]),
@@ -374,14 +377,16 @@ class BgzfWriter:
         if load().dcr_bgzw_put_blocks(self._h, blocks.ctypes.data, blocks.nbytes, raw_bytes) != 0:
             raise _err("BGZF put_blocks")
 
-    def write_consensus(self, hb: HostBatch, ss: FmtOut, ds: FmtOut, n_fam: int):
-        if n_fam and load().dcr_fmt_write(self._h, ctypes.byref(hb.s), ctypes.byref(ss), ctypes.byref(ds),
-                                          n_fam) != 0:
+    def write_consensus(self, hb: HostBatch, ss: FmtOut, ds: FmtOut, n_fam: int, fam_filt=None):
+        """``fam_filt`` (apply_filter): the families it drops are skipped."""
+        if n_fam and load().dcr_fmt_write_filt(self._h, ctypes.byref(hb.s), ctypes.byref(ss), ctypes.byref(ds), n_fam,
+                                               fam_filt.ctypes.data if fam_filt is not None else None) != 0:
             raise _err("consensus write")
 
-    def write_consensus_ss(self, hb: HostBatch, ss: FmtOut, n_fam: int):
+    def write_consensus_ss(self, hb: HostBatch, ss: FmtOut, n_fam: int, fam_filt=None):
         """The four single-strand records of families [0, n_fam) (dcr_fmt_write_ss)."""
-        if n_fam and load().dcr_fmt_write_ss(self._h, ctypes.byref(hb.s), ctypes.byref(ss), n_fam) != 0:
+        if n_fam and load().dcr_fmt_write_ss_filt(self._h, ctypes.byref(hb.s), ctypes.byref(ss), n_fam,
+                                                  fam_filt.ctypes.data if fam_filt is not None else None) != 0:
             raise _err("single-strand consensus write")
 
     def write_synthetic(self, packed, umis, fam_id0=0, tid=0, n_threads=0):
@@ -426,6 +431,19 @@ def first_failure(hb: HostBatch, ss: FmtOut, ds: FmtOut, n_fam: int, read_status
     f = load().dcr_fmt_scan(ctypes.byref(hb.s), ctypes.byref(ss), ctypes.byref(ds), rs, n_fam,
                             ctypes.byref(kind), ctypes.byref(which))
     return f, FAIL_NAMES.get(kind.value), which.value
+
+
+def apply_filter(hb: HostBatch, ss: FmtOut, ds: FmtOut, flt, n_fam: int) -> np.ndarray:
+    """dcr_fmt_filter: the consensus filter ``flt`` (params.ConsensusFilter)
+    over processed families [0, n_fam), none of which fails.  Masks the
+    duplex seq / qual arrays in place; returns fam_filt[n_fam] (low byte:
+    reason bits, not 0 = dropped; bits 8 and up: bases masked)."""
+    out = np.zeros(max(n_fam, 1), np.int32)
+    s = flt.as_struct()
+    if load().dcr_fmt_filter(ctypes.byref(hb.s), ctypes.byref(ss), ctypes.byref(ds), ctypes.byref(s), n_fam,
+                             out.ctypes.data) != 0:
+        raise _err("consensus filter")
+    return out[:n_fam]
 
 
 def deflate_emulate(data: bytes) -> bytes:

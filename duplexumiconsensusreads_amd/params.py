@@ -159,3 +159,101 @@ def build_dcr_params(p: ConsensusParams) -> DcrParams:
         s.qthresh[i] = t
     _CACHE[p] = s
     return s
+
+
+# ---- consensus filters (include/dcr.h dcr_filter; not reference flags) ----------
+FILT_MIN_READS, FILT_ERROR_RATE, FILT_NO_CALL, FILT_MEAN_QUAL, FILT_MASK_BASES = 1, 2, 4, 8, 16
+FILT_REASONS = ((FILT_MIN_READS, "min_reads"), (FILT_ERROR_RATE, "max_read_error_rate"),
+                (FILT_NO_CALL, "max_no_call_fraction"), (FILT_MEAN_QUAL, "min_mean_base_quality"))
+
+
+class DcrFilter(ctypes.Structure):
+    """Mirror of ``dcr_filter`` (include/dcr.h)."""
+    _fields_ = [("active", ctypes.c_int32), ("min_base_quality", ctypes.c_int32),
+                ("min_reads", ctypes.c_int32 * 3), ("reserved0", ctypes.c_int32),
+                ("max_error_rate", ctypes.c_double * 2), ("max_no_call_fraction", ctypes.c_double),
+                ("min_mean_base_quality", ctypes.c_double)]
+
+
+def _numbers(text, conv, most, what):
+    parts = text.split(",")
+    if not 1 <= len(parts) <= most:
+        raise ValueError(f"{what}: 1 to {most} comma-separated values, got {text!r}")
+    vals = [conv(p) for p in parts]          # ValueError on a malformed number
+    return vals + [vals[-1]] * (most - len(vals))
+
+
+def filter_min_base_quality(text):
+    v = int(text)
+    if v < 0:
+        raise ValueError("--filter_min_base_quality must be >= 0")
+    return v
+
+
+def filter_min_reads(text):
+    """``T[,A[,B]]``: missing values repeat the last; T >= A >= B."""
+    t, a, b = _numbers(text, int, 3, "--filter_min_reads")
+    if not (t >= a >= b):
+        raise ValueError("--filter_min_reads T,A,B needs T >= A >= B")
+    return (t, a, b)
+
+
+def _unit(text):
+    v = float(text)
+    if not 0.0 <= v <= 1.0:                   # NaN fails too
+        raise ValueError(f"{text!r} is not in [0, 1]")
+    return v
+
+
+def filter_max_read_error_rate(text):
+    """``C[,S]``: duplex and single-strand bounds; S defaults to C."""
+    return tuple(_numbers(text, _unit, 2, "--filter_max_read_error_rate"))
+
+
+def filter_max_no_call_fraction(text):
+    return _unit(text)
+
+
+def filter_min_mean_base_quality(text):
+    v = float(text)
+    if not 0.0 <= v < math.inf:
+        raise ValueError("--filter_min_mean_base_quality must be a finite number >= 0")
+    return v
+
+
+@dataclasses.dataclass(frozen=True)
+class ConsensusFilter:
+    """The ``--filter_*`` options, parsed; None = that rule is off."""
+    min_base_quality: object = None          # int
+    min_reads: object = None                 # (T, A, B)
+    max_read_error_rate: object = None       # (C, S)
+    max_no_call_fraction: object = None      # float
+    min_mean_base_quality: object = None     # float
+
+    @classmethod
+    def from_args(cls, args):
+        """The filter of a parsed command line, or None when no option is given."""
+        f = cls(args.filter_min_base_quality, args.filter_min_reads, args.filter_max_read_error_rate,
+                args.filter_max_no_call_fraction, args.filter_min_mean_base_quality)
+        return f if f.active else None
+
+    @property
+    def active(self) -> int:
+        return ((FILT_MASK_BASES if self.min_base_quality is not None else 0)
+                | (FILT_MIN_READS if self.min_reads is not None else 0)
+                | (FILT_ERROR_RATE if self.max_read_error_rate is not None else 0)
+                | (FILT_NO_CALL if self.max_no_call_fraction is not None else 0)
+                | (FILT_MEAN_QUAL if self.min_mean_base_quality is not None else 0))
+
+    def as_struct(self) -> DcrFilter:
+        s = DcrFilter()
+        s.active = self.active
+        s.min_base_quality = min(self.min_base_quality or 0, 256)     # quality bytes are below 256
+        clamp = lambda v: max(-(1 << 31), min(v, (1 << 31) - 1))      # noqa: E731
+        for i, v in enumerate(self.min_reads or (0, 0, 0)):
+            s.min_reads[i] = clamp(v)
+        for i, v in enumerate(self.max_read_error_rate or (0.0, 0.0)):
+            s.max_error_rate[i] = v
+        s.max_no_call_fraction = self.max_no_call_fraction or 0.0
+        s.min_mean_base_quality = self.min_mean_base_quality or 0.0
+        return s

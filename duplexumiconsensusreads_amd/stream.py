@@ -130,7 +130,9 @@ class _WriterOut:
         self.small = None
         self.blocks = None
 
-    def ensure(self, n_fam, bgzf_bytes):
+        self.filt = None                 # pinned fam_filt, made when a filter is first set
+
+    def ensure(self, n_fam, bgzf_bytes, filt=False):
         if n_fam > self.cap_f or self.small is None:
             self.cap_f = int(n_fam * 1.25) + 64
             self.small = Pinned(self.lib, 12 * self.cap_f + 64)
@@ -138,6 +140,9 @@ class _WriterOut:
             self.fam_fail = a[:4 * self.cap_f].view(np.int32)
             self.ds_len = a[4 * self.cap_f:12 * self.cap_f].view(np.int32)
             self.totals = a[12 * self.cap_f:12 * self.cap_f + 24].view(np.int64)
+        if filt and (self.filt is None or self.filt.nbytes < 4 * self.cap_f):
+            self.filt = Pinned(self.lib, 4 * self.cap_f)
+            self.fam_filt = self.filt.array.view(np.int32)
         if bgzf_bytes > self.cap_b:
             self.cap_b = int(bgzf_bytes * 1.25) + (1 << 20)
             self.blocks = Pinned(self.lib, self.cap_b)
@@ -154,11 +159,14 @@ class WriterResult:
     duplex lengths, and the BGZF blocks of the records of every family that
     does not fail.  With the single-strand stream (dcr_submit_write_ss) also
     ``ss_bgzf`` / ``ss_record_bytes``: the blocks of those families' four
-    single-strand records; None without it."""
+    single-strand records; None without it.  With a consensus filter set
+    ``fam_filt``: the per-family outcome words (low byte not 0: dropped, its
+    records are not in the streams); None without one."""
 
-    def __init__(self, stream, slot, out, n_fam, out_ss=None):
+    def __init__(self, stream, slot, out, n_fam, out_ss=None, filtered=False):
         self._stream, self._slot = stream, slot
         self.fam_fail = out.fam_fail[:n_fam]
+        self.fam_filt = out.fam_filt[:n_fam] if filtered else None
         self.ds_len = out.ds_len[:2 * n_fam]
         self.bgzf_bytes, self.record_bytes, self.blocks = (int(x) for x in out.totals[:3])
         self.bgzf = out.blocks.array[:self.bgzf_bytes]
@@ -194,7 +202,11 @@ class DeviceStream:
     ``ss_output`` (set per run, cli.main): the single-strand records are
     wanted too: host batches carry their metadata, the device writer makes
     their stream (dcr_submit_write_ss) and the host path downloads their pos,
-    n_cig and cigar."""
+    n_cig and cigar.
+
+    ``filter`` (set per run too): a params.ConsensusFilter or None.  The
+    device writer applies it (dcr_set_filter) and ``result`` carries
+    ``fam_filt``; on the host path the caller filters (native_io.apply_filter)."""
 
     def __init__(self, ctx, n_slots=2, owns_ctx=False, device_writer=True, persistent=False):
         """``persistent``: ``close`` only drains the slots (the context and the
@@ -208,6 +220,7 @@ class DeviceStream:
         self._spare = {}                 # reads -> [HostBatch] released by earlier runs
         self.device_writer = device_writer
         self.ss_output = False
+        self.filter = None
         self.wouts_ss = None
         self.lib = _lib.load()
         self.n_slots = n_slots
@@ -240,7 +253,12 @@ class DeviceStream:
             from . import _lib
             wo = self.wouts[slot]
             # compressed records are far smaller than the kernel outputs; grown on demand
-            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3))
+            filtered = self.filter is not None
+            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered)
+            # the context may serve other streams: its filter is this stream's for this batch
+            self.ctx.set_filter(self.filter)
+            if filtered:
+                _lib._check(self.lib.dcr_slot_filter_out(self.ctx._ctx, slot, wo.filt.ptr))
             self._b = hb.batch_struct()
             m = WMeta()
             m.names, m.n_names = hb.a["names"].ctypes.data, s.n_names
@@ -260,11 +278,11 @@ class DeviceStream:
                                                          ctypes.byref(ms), ctypes.byref(self._wres),
                                                          ctypes.byref(self._wres_ss)))
                 self.busy[slot] = True
-                return (slot, s.n_fam, True)
+                return (slot, s.n_fam, True, filtered)
             _lib._check(self.lib.dcr_submit_write(self.ctx._ctx, slot, ctypes.byref(self._b), ctypes.byref(m),
                                                   ctypes.byref(self._wres)))
             self.busy[slot] = True
-            return (slot, s.n_fam)
+            return (slot, s.n_fam, False, filtered)
         out = self.outs[slot]
         out.ensure(4 * s.n_fam, s.ss_cols, 2 * s.n_fam, s.ds_cols, s.n_reads,
                    SS_FIELDS_FULL if self.ss_output else SS_FIELDS)
@@ -281,7 +299,7 @@ class DeviceStream:
         if self.device_writer:
             slot, n_fam = handle[:2]
             wo = self.wouts[slot]
-            ws = self.wouts_ss[slot] if len(handle) > 2 else None
+            ws = self.wouts_ss[slot] if handle[2] else None
             r = wo.wres()
             if ws is not None:
                 rc = self.lib.dcr_wait_write_ss(self.ctx._ctx, slot, ctypes.byref(r), ctypes.byref(ws.wres()))
@@ -299,7 +317,7 @@ class DeviceStream:
                     grown = True
             if not grown:
                 _lib._check(rc)
-            return WriterResult(self, slot, wo, n_fam, ws)
+            return WriterResult(self, slot, wo, n_fam, ws, handle[3])
         slot = handle
         _lib._check(self.lib.dcr_wait(self.ctx._ctx, slot))
         self.busy[slot] = False
@@ -327,7 +345,7 @@ class DeviceStream:
             if o.mem is not None:
                 o.mem.free()
         for w in self.wouts + (self.wouts_ss or []):
-            for m in (w.small, w.blocks):
+            for m in (w.small, w.blocks, w.filt):
                 if m is not None:
                     m.free()
         if self.owns_ctx:
@@ -340,6 +358,7 @@ class CallBackend:
     def __init__(self, fn, params):
         self.fn, self.params = fn, params
         self.ss_output = False
+        self.filter = None               # applied by the caller (native_io.apply_filter)
         self._res = {}
         self._k = 0
 

@@ -241,6 +241,49 @@ int dcr_submit_write_ss(dcr_ctx *ctx, int slot, const dcr_batch *host_in, const 
                         const dcr_wmeta_ss *meta_ss, dcr_wres *res, dcr_wres *res_ss);
 int dcr_wait_write_ss(dcr_ctx *ctx, int slot, dcr_wres *res, dcr_wres *res_ss);
 
+/* Consensus filters (not a reference feature; the step fgbio's
+ * FilterConsensusReads does on the written file).  With a filter set on the
+ * context, dcr_submit_write[_ss] first masks, in the slot's duplex seq / qual,
+ * every base of a family that does not fail whose quality is below
+ * min_base_quality ('N', quality min(q, 2)), then tests both duplex records
+ * k = 2f + j (built from single-strand records a = 4f + 2j, b = a + 1) against
+ * the active rules.  A family is written iff both records pass every rule;
+ * a dropped family's records (and its four single-strand records) get size 0.
+ *   DCR_FILT_MIN_READS  D[a] + D[b] >= min_reads[0], max >= [1], min >= [2]
+ *   DCR_FILT_ERROR_RATE ds.E[k] <= max_error_rate[0], ss.E[a], ss.E[b] <= [1]
+ *                       (IEEE compares: NaN fails)
+ *   DCR_FILT_NO_CALL    !( (double)n > max_no_call_fraction * (double)len ),
+ *                       n = 'N' bases after masking
+ *   DCR_FILT_MEAN_QUAL  !( (double)s < min_mean_base_quality * (double)len ),
+ *                       s = sum of the qualities after masking
+ * (one double multiply each, no fused contraction).  The per-family outcome
+ * word fam_filt[f]: low byte = the DCR_FILT_* bits of the rules that failed
+ * (1 min_reads, 2 error rate, 4 no-call fraction, 8 mean quality), the union
+ * over both records; bits 8 and up = bases masked in the family's two records; 0 for
+ * failing families, which are not filtered. */
+#define DCR_FILT_MIN_READS 1     /* active bits; the first four are also reason bits */
+#define DCR_FILT_ERROR_RATE 2
+#define DCR_FILT_NO_CALL 4
+#define DCR_FILT_MEAN_QUAL 8
+#define DCR_FILT_MASK_BASES 16
+typedef struct dcr_filter {
+    int32_t active;               /* DCR_FILT_* bits; 0: no filter             */
+    int32_t min_base_quality;     /* DCR_FILT_MASK_BASES                       */
+    int32_t min_reads[3];         /* total, larger strand, smaller strand      */
+    int32_t reserved0;
+    double max_error_rate[2];     /* duplex, single strand                     */
+    double max_no_call_fraction;
+    double min_mean_base_quality;
+} dcr_filter;
+/* NULL or active == 0: off (the default; nothing is launched or copied).
+ * Holds for the batches submitted after the call. */
+int dcr_set_filter(dcr_ctx *ctx, const dcr_filter *filter);
+/* Where a slot's fam_filt[F] goes (pinned host memory, at least n_fam int32
+ * of every batch submitted on the slot while a filter is set): copied with
+ * fam_fail, on the same stream and before the same event, so it is complete
+ * when dcr_wait_write[_ss] returns.  NULL removes it. */
+int dcr_slot_filter_out(dcr_ctx *ctx, int slot, int32_t *fam_filt);
+
 /* CPU restatement with the same contract (oracle/, test infrastructure):
    host pointers, single thread (or n_threads > 1) */
 int dcr_oracle_run(const dcr_params *params, const dcr_batch *in, dcr_out *ss, dcr_out *ds,

@@ -259,6 +259,22 @@ int dcr_fmt_write(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, 
  * and sub_rx (DCR_INGEST_SS_META); ss holds every field of dcr_fmt_out. */
 int dcr_fmt_write_ss(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, int32_t n_fam);
 
+/* The consensus filters on the host (include/dcr.h dcr_filter states the
+ * rules; the device's k_filter gives the same bytes and words).
+ * dcr_fmt_filter applies *filter to processed families [0, n_fam), none of
+ * which fails: it masks ds->seq / ds->qual IN PLACE (the arrays are written
+ * through the const pointers) and fills fam_filt[0, n_fam): low byte = reason
+ * bits (dropped when not 0), bits 8 and up = bases masked.  The _filt write
+ * entries are dcr_fmt_write / dcr_fmt_write_ss without the records of the
+ * families whose fam_filt low byte is set (fam_filt NULL: every family). */
+struct dcr_filter;
+int dcr_fmt_filter(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds,
+                   const struct dcr_filter *filter, int32_t n_fam, int32_t *fam_filt);
+int dcr_fmt_write_filt(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds,
+                       int32_t n_fam, const int32_t *fam_filt);
+int dcr_fmt_write_ss_filt(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, int32_t n_fam,
+                          const int32_t *fam_filt);
+
 /* ---- the GPU BGZF block compressor (csrc/dcr_deflate.h) emulated lane by
  * lane on the host, for tests: one BGZF block of in[0, n) (n <= 0xff00) into
  * out (>= 64 KiB); returns its size or -1 */
