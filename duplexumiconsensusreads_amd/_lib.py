@@ -48,6 +48,8 @@ EXPORTS = {
                                       ctypes.c_void_p]),
     "dcr_set_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "dcr_slot_filter_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "dcr_set_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "dcr_slot_metrics_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     # include/dcr_inflate.h: BGZF inflate on the device
     "dcr_inflater_create": (ctypes.c_void_p, [ctypes.c_int]),
     "dcr_inflater_destroy": (None, [ctypes.c_void_p]),
@@ -123,6 +125,7 @@ class Context:
             raise DcrError(f"dcr_create failed: {lib.dcr_last_error().decode()}")
         self.want_info = want_info
         self.filter = None
+        self.metrics = False
         if want_info:
             _check(lib.dcr_set_options(self._ctx, 1))
 
@@ -150,6 +153,14 @@ class Context:
         s = flt.as_struct() if flt is not None else None
         _check(load().dcr_set_filter(self._ctx, ctypes.byref(s) if s is not None else None))
         self.filter = flt
+
+    def set_metrics(self, on):
+        """The device writer counts the consensus QC tables (dcr_metrics) for
+        the batches it takes from now on, or not (dcr_set_metrics)."""
+        if bool(on) == self.metrics:
+            return
+        _check(load().dcr_set_metrics(self._ctx, 1 if on else 0))
+        self.metrics = bool(on)
 
     @property
     def stream(self):

@@ -23,6 +23,11 @@ families whose duplex records have too little support or too many
 disagreements (include/dcr.h ``dcr_filter``): the step that otherwise follows
 on the written file.  Off by default; without one nothing changes.
 
+``--metrics_output FILE.json`` (not a reference flag) writes the consensus QC
+tables (include/dcr.h ``dcr_metrics``): family sizes, strand depths, error
+rates, base qualities and errors by read position of the consensus as called,
+before any filter; counted on the device beside the writer.  Off by default.
+
 Batches are pipelined: a thread ingests batch k+1 while the device runs batch
 k and the main thread writes batch k-1.
 
@@ -107,6 +112,10 @@ def parse_args(argv):
     ap.add_argument("--filter_min_mean_base_quality", required=False, default=None, metavar="Q",
                     type=params_mod.filter_min_mean_base_quality,
                     help="keep a duplex read whose mean base quality after masking is at least Q")
+    # not a reference flag: the consensus QC tables (include/dcr.h dcr_metrics) as JSON
+    ap.add_argument("--metrics_output", required=False, default=None, type=str, metavar="FILE.json",
+                    help="count family sizes, strand depths, error rates, qualities and errors by read position "
+                         "of the consensus reads as called (before any --filter_*) into FILE.json")
     return ap.parse_args(argv)
 
 
@@ -249,11 +258,11 @@ def gpu_inflate(device: int = 0):
     return got[0]
 
 
-def _as_backend(backend, params, device=0, ss_output=False, flt=None):
+def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=False):
     """``ss_output``: this run also writes the single-strand records (a
     property of the run, set on the backend each time: the default backend
     is kept across runs).  ``flt``: this run's ConsensusFilter or None,
-    set each time in the same way."""
+    set each time in the same way; so is ``metrics`` (--metrics_output)."""
     if backend is None:
         be = default_backend(params, device)
     elif hasattr(backend, "submit"):
@@ -269,6 +278,10 @@ def _as_backend(backend, params, device=0, ss_output=False, flt=None):
         be.filter = flt
     elif flt is not None:
         raise ValueError("this backend cannot apply the consensus filters")
+    if hasattr(be, "metrics"):
+        be.metrics = metrics
+    elif metrics:
+        raise ValueError("this backend cannot count the consensus metrics")
     return be
 
 
@@ -282,6 +295,32 @@ def _check_ss_output(args, say=True):
         if say:
             print(OUTPUT_FORMAT_ERROR)
         raise ReferenceExit(1)
+
+
+def _check_metrics_output(args, say=True):
+    """--metrics_output must name a .json file; it is created here, before
+    the pass and before any output file, so a bad path fails early."""
+    path = args.metrics_output
+    if path is None:
+        return
+    if not path.endswith(".json"):
+        if say:
+            print(OUTPUT_FORMAT_ERROR)
+        raise ReferenceExit(1)
+    open(path, "a").close()
+
+
+def _finish_metrics(path, total, done):
+    """The run's counters as JSON when it completed; otherwise no file (the
+    counters of the families after a failing one cannot be separated out)."""
+    if path is None:
+        return
+    if done and total is not None:
+        with open(path, "w") as f:
+            f.write(params_mod.metrics_json(total))
+    else:
+        with contextlib.suppress(OSError):
+            os.remove(path)
 
 
 def _raise_reference(kind: str, msg: str = ""):
@@ -311,6 +350,8 @@ class _Driver:
                       "submit_s": 0.0, "wait_s": 0.0, "write_s": 0.0, "idle_s": 0.0}
         if self.filter is not None:
             self.stats.update(filter_dropped_families=0, filter_masked_bases=0)
+        # --metrics_output: the batches' counters summed at once (a device slot's block is overwritten on reuse)
+        self.metrics_total = np.zeros(params_mod.MET_WORDS, np.uint64) if args.metrics_output is not None else None
 
     # -- stdout of one batch, in the reference's order --------------------------
     def _prints(self, hb, fail_f, kind, which, last_batch):
@@ -451,10 +492,15 @@ class _Driver:
                     self.sscs.write(res.ss_record_bytes_of(fail_f))
             lens = res.ds_len[:2 * fail_f]
             filt = res.fam_filt[:fail_f] if self.filter is not None else None
+            if self.metrics_total is not None:
+                self.metrics_total += res.metrics
         else:
             ss, ds, rstat = res
             fail_f, kind, which = native_io.first_failure(hb, ss, ds, F, rstat)
             self._prints(hb, fail_f, kind, which, last_batch)
+            if self.metrics_total is not None:
+                # before the filter, which masks the duplex arrays in place
+                self.metrics_total += native_io.metrics(hb, ss, ds, fail_f)
             filt = native_io.apply_filter(hb, ss, ds, self.filter, fail_f) if self.filter is not None else None
             self.cons.write_consensus(hb, ss, ds, fail_f, filt)
             if self.sscs is not None:
@@ -636,15 +682,28 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
         raise ReferenceExit(1)
     _check_ss_output(args)
     ss_path = args.single_strand_output
-    be = _as_backend(backend, params, args.device, ss_path is not None, ConsensusFilter.from_args(args))
-    cons, excl, unproc, *rest = _open_writers(
-        [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
-         "%s_filteredfamilies.bam" % consensus_filename[:-4]] + ([ss_path] if ss_path else []), ing.header, args, ing)
+    try:
+        _check_metrics_output(args)
+    except BaseException:
+        ing.close()
+        raise
+    met_path, met_total, done = args.metrics_output, None, False
+    try:
+        be = _as_backend(backend, params, args.device, ss_path is not None, ConsensusFilter.from_args(args),
+                         met_path is not None)
+        cons, excl, unproc, *rest = _open_writers(
+            [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
+             "%s_filteredfamilies.bam" % consensus_filename[:-4]] + ([ss_path] if ss_path else []), ing.header, args,
+            ing)
+    except BaseException:
+        _finish_metrics(met_path, None, False)      # no empty metrics file from a run that never started
+        raise
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng.getstate())
     t_open = time.perf_counter()
     try:
         drv = _Driver(args, params, be, ing, cons, excl, unproc, sscs)
+        met_total = drv.metrics_total
         if stats is not None and "trace" in stats:
             drv.trace = stats["trace"]
         try:
@@ -661,6 +720,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
         if args.verbose:
             print("\n Input file has been completely read \n")
         _print_summary(c)
+        done = True
     finally:
         t_close = time.perf_counter()
         try:
@@ -670,7 +730,10 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
                 _close_all(excl.close, unproc.close, cons.close, *((sscs.close,) if sscs else ()))
             finally:
                 t_wclose = time.perf_counter()
-                ing.close()
+                try:
+                    ing.close()
+                finally:
+                    _finish_metrics(met_path, met_total, done)
         if stats is not None:
             stats["close_s"] = time.perf_counter() - t_close
             stats["close_writers_s"] = t_wclose - t_close
@@ -826,7 +889,8 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
     ing = native_io.Ingest(path, params.min_map_quality, params.min_reads, params.max_reads,
                            params.min_base_quality, args.threads, rng_range[0], rng_range[1],
                            ss_meta=len(parts) > 3)
-    be = _as_backend(backend, params, device, len(parts) > 3, ConsensusFilter.from_args(args))
+    be = _as_backend(backend, params, device, len(parts) > 3, ConsensusFilter.from_args(args),
+                     args.metrics_output is not None)
     cons, excl, unproc, *rest = _open_writers(parts, header, args, ing)
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng_state)
@@ -846,6 +910,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
     finally:
         res["calls"] = ing.sample_calls()
         res["counters"] = dict(ing.counters(), **drv.filter_counts)
+        res["metrics"] = drv.metrics_total
         res["stats"] = dict(drv.stats)
         res["stdout"] = out.getvalue()
         try:
@@ -1143,6 +1208,7 @@ def _main_sharded(args, params, backend, rng, stats, group):
             print(OUTPUT_FORMAT_ERROR)
         raise ReferenceExit(1)
     _check_ss_output(args, say=rank == 0)
+    _check_metrics_output(args, say=rank == 0)      # every rank: a bad path ends them all before any collective
     finals = [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
               "%s_filteredfamilies.bam" % consensus_filename[:-4]]
     if args.single_strand_output is not None:
@@ -1238,7 +1304,15 @@ def _main_sharded(args, params, backend, rng, stats, group):
         if args.verbose:
             print("\n Input file has been completely read \n")
         _print_summary(tot)
+        if args.metrics_output is not None:
+            # integer sums: the ranks' totals add up to the single-process run's
+            met = np.zeros(params_mod.MET_WORDS, np.uint64)
+            for r in range(min(world, len(ranges))):
+                if results[r].get("metrics") is not None:
+                    met += results[r]["metrics"]
+            _finish_metrics(args.metrics_output, met, True)
         return 0
+    _finish_metrics(args.metrics_output, None, False)
     st, ea = results[fail]["status"], results[fail]["exc_args"]
     if st == "exit":
         raise ReferenceExit(*ea)

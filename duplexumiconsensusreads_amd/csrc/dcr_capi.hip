@@ -218,6 +218,7 @@ struct WriterBufs {
     int64_t *tot;
     uint32_t *tok;
     int32_t *fam_filt;      // k_filter's outcomes; null unless a filter is set (dcr_set_filter)
+    dcr_metrics *metrics;   // k_metrics' accumulator; null unless metrics are on (dcr_set_metrics)
 };
 
 // The second stream of dcr_submit_write_ss: the single-strand records'
@@ -239,9 +240,10 @@ struct WriterSsBufs {
 // F families, n_names bytes of names, a record stream of at most B bytes in
 // at most nbm blocks, gd k_deflate workgroups; with ws, the single-strand
 // stream's regions after them (the first stream's layout does not change)
-// and with filt, k_filter's outcomes (no region without it)
+// and with filt, k_filter's outcomes (no region without it); with met,
+// k_metrics' accumulator (none without it)
 void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w,
-                 WriterSsBufs *ws = nullptr, bool filt = false) {
+                 WriterSsBufs *ws = nullptr, bool filt = false, bool met = false) {
     w.names = p.take<char>((size_t)n_names + 1);
     w.fam_code = p.take<int64_t>((size_t)F);
     w.fam_rx = p.take<int64_t>(2 * (size_t)F);
@@ -259,6 +261,7 @@ void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd
     w.tot = p.take<int64_t>(4);
     w.tok = p.take<uint32_t>((size_t)gd * dfl::kTokWords);
     w.fam_filt = filt ? p.take<int32_t>((size_t)F) : nullptr;
+    w.metrics = met ? p.take<dcr_metrics>(1) : nullptr;
     if (!ws) return;
     ws->sub_flag = p.take<uint16_t>(4 * (size_t)F);
     ws->sub_mi = p.take<int64_t>(4 * (size_t)F);
@@ -317,6 +320,7 @@ struct dcr_ctx {
         hipEvent_t ev_h2d = nullptr, ev_comp = nullptr, ev_d2h = nullptr;
         int *h_err = nullptr;     // pinned copy of the batch's capacity flag
         int32_t *h_fam_filt = nullptr;   // the caller's pinned fam_filt (dcr_slot_filter_out), or null
+        dcr_metrics *h_metrics = nullptr;   // the caller's pinned counters (dcr_slot_metrics_out), or null
         bool busy = false;
     } slots[DCR_MAX_SLOTS];
     dcr::Workspace w{};
@@ -327,6 +331,7 @@ struct dcr_ctx {
     int wide_ok = 0;    // the general kernel's decision pass may run (wide_table)
     dcr_params host_params{};
     dcr_filter filter{};    // dcr_set_filter; active == 0: off
+    bool metrics = false;   // dcr_set_metrics
     // fast-kernel constants (fast_constants)
     uint32_t fast_kq = 0, fast_kqlo = 0;
     int fast_maxq = 0, fast_t16 = 0, fast_r_safe = 0, fast_qlo = 0;
@@ -1005,11 +1010,14 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     const bool filt = c->filter.active != 0;
     if (filt && F && !S.h_fam_filt)
         return fail(DCR_EARG, "a filter is set but the slot has no fam_filt destination (dcr_slot_filter_out)");
+    const bool met = c->metrics;
+    if (met && !S.h_metrics)
+        return fail(DCR_EARG, "metrics are on but the slot has no destination (dcr_slot_metrics_out)");
     Plan wsz;
-    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt);
+    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met);
     if (wsz.off > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wsz.off + wsz.off / 8));
     Plan wp{(char *)S.wbuf.p};
-    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt);
+    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met);
     // H2D: inputs and writer metadata on the copy stream
     HIP_TRY(upload_inputs(h, db, c->s_h2d));
     if (m->n_names) HIP_TRY(hipMemcpyAsync(wb.names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
@@ -1046,8 +1054,19 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     A.fam_filt = wb.fam_filt;
     HIP_TRY(hipMemsetAsync(wb.rec_size, 0, 8 * (size_t)(2 * F + 1), c->stream));
     HIP_TRY(hipMemsetAsync(wb.bsz, 0, 8 * (size_t)(nbm + 2), c->stream));
+    // the slot's counters start from zero for every batch (an empty batch gives zeros)
+    if (met) HIP_TRY(hipMemsetAsync(wb.metrics, 0, sizeof(dcr_metrics), c->stream));
     if (F) {
         hipLaunchKernelGGL(dcrw::k_famfail, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, c->stream, A);
+        if (met) {
+            // one wave per family, before k_filter masks the duplex seq / qual; at most one
+            // workgroup per CU: every workgroup ends with a global add per non-zero bin
+            dcrw::MetricsArgs Ma{dout[0], dout[1], db.sub_off, db.ss_col_off, db.ds_col_off, wb.fam_fail, (int32_t)F,
+                                 wb.metrics};
+            const int wpg = dcrw::kMetThreads / 64;
+            const unsigned gm = (unsigned)std::max<int64_t>(1, std::min<int64_t>((F + wpg - 1) / wpg, (int64_t)c->n_cu));
+            hipLaunchKernelGGL(dcrw::k_metrics, dim3(gm), dim3(dcrw::kMetThreads), 0, c->stream, Ma);
+        }
         if (filt) {
             // one wave per family, before anything reads the duplex seq / qual
             dcrw::FilterArgs Fa{dout[0], dout[1], db.ds_col_off, wb.fam_fail, wb.fam_filt, (int32_t)F, c->filter};
@@ -1120,6 +1139,7 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         HIP_TRY(hipMemcpyAsync(res->ds_len, wb.ds_len, 8 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
         if (filt) HIP_TRY(hipMemcpyAsync(S.h_fam_filt, wb.fam_filt, 4 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
     }
+    if (met) HIP_TRY(hipMemcpyAsync(S.h_metrics, wb.metrics, sizeof(dcr_metrics), hipMemcpyDeviceToHost, c->s_d2h));
     HIP_TRY(hipMemcpyAsync(res->totals, wb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
     if (ms) HIP_TRY(hipMemcpyAsync(res_ss->totals, wsb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
     HIP_TRY(hipEventRecord(S.ev_d2h, c->s_d2h));
@@ -1162,6 +1182,19 @@ int dcr_slot_filter_out(dcr_ctx *c, int slot, int32_t *fam_filt) {
     if (!c || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
     if (c->slots[slot].busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
     c->slots[slot].h_fam_filt = fam_filt;
+    return DCR_OK;
+}
+
+int dcr_set_metrics(dcr_ctx *c, int on) {
+    if (!c) return fail(DCR_EARG, "NULL context");
+    c->metrics = on != 0;
+    return DCR_OK;
+}
+
+int dcr_slot_metrics_out(dcr_ctx *c, int slot, dcr_metrics *pinned_dst) {
+    if (!c || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
+    if (c->slots[slot].busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
+    c->slots[slot].h_metrics = pinned_dst;
     return DCR_OK;
 }
 

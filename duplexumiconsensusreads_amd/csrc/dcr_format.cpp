@@ -11,6 +11,7 @@
 //   pysam typing         smallest integer type, 'f' float32, 'Z' text, 'B' arrays;
 //                        sd/se text is str() of a list of numpy-1.x ints: "[1, 2]"
 #include <cctype>
+#include <cmath>
 #include <fcntl.h>
 #include <unistd.h>
 #include <cstdio>
@@ -639,6 +640,60 @@ int dcr_fmt_filter(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fm
                 why |= DCR_FILT_MEAN_QUAL;
         }
         fam_filt[f] = (int32_t)(why | (masked << 8));
+    }
+    return DCR_IO_OK;
+}
+
+// the tables of include/dcr.h (dcr_metrics), as dcr_writer.hip's k_metrics counts them
+static int met_err_bin(double E) {
+    // one double multiply (built with -ffp-contract=off); NaN fails both compares
+    return (E >= 0.0 && E <= 1.0) ? (int)std::rint(E * 1000.0) : DCR_MET_ERR_BINS - 1;
+}
+
+int dcr_fmt_metrics(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds, int32_t n_fam,
+                    const int32_t *fam_fail, dcr_metrics *m) {
+    if (!hb || !ss || !ds || !m || n_fam < 0 || n_fam > hb->n_fam) return fail(DCR_IO_EARG, "bad arguments");
+    auto clampi = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : v > hi ? hi : v; };
+    auto columns = [&](int kind, bool rev, const uint16_t *d, const uint16_t *e, int64_t n) {
+        for (int64_t c = 0; c < n; ++c) {
+            const int64_t cp = rev ? n - 1 - c : c;
+            const int64_t b = cp < DCR_MET_COL_BINS - 1 ? cp : DCR_MET_COL_BINS - 1;
+            m->col[kind][0][b] += 1;
+            m->col[kind][1][b] += d[c];
+            m->col[kind][2][b] += e[c];
+        }
+    };
+    for (int32_t f = 0; f < n_fam; ++f) {
+        if (fam_fail && fam_fail[f] != 0) continue;
+        m->n[0] += 1;
+        for (int k = 0; k < 4; ++k) {
+            const int32_t s = 4 * f + k;
+            const int64_t ro = hb->ss_col_off[s], room = hb->ss_col_off[s + 1] - ro;
+            const int64_t L = clampi(ss->len[s], room), N = clampi(ss->n_de[s], room);
+            m->n[1] += (uint64_t)L;
+            m->n[4] += (uint64_t)N;
+            const int64_t nr = clampi((int64_t)hb->sub_off[s + 1] - hb->sub_off[s], DCR_MET_READS_BINS - 1);
+            m->ss_reads[k][nr] += 1;
+            for (int64_t i = 0; i < L; ++i) m->ss_qual[ss->qual[ro + i]] += 1;
+            columns(0, k >= 2, ss->d + ro, ss->e + ro, N);
+        }
+        for (int j = 0; j < 2; ++j) {
+            const int32_t r = 2 * f + j, a = 4 * f + 2 * j, b = a + 1;
+            const int64_t ro = hb->ds_col_off[r], room = hb->ds_col_off[r + 1] - ro;
+            const int64_t L = clampi(ds->len[r], room), N = clampi(ds->n_de[r], room);
+            m->n[2] += (uint64_t)L;
+            m->n[5] += (uint64_t)N;
+            const int64_t aD = clampi(ss->D[a], DCR_MET_DEPTH_BINS - 1), bD = clampi(ss->D[b], DCR_MET_DEPTH_BINS - 1);
+            m->ds_depth[aD > bD ? aD : bD][aD > bD ? bD : aD] += 1;
+            m->err_c[met_err_bin(ds->E[r])] += 1;
+            const int ea = met_err_bin(ss->E[a]), eb = met_err_bin(ss->E[b]);
+            m->err_s[ea > eb ? ea : eb] += 1;
+            for (int64_t i = 0; i < L; ++i) {
+                m->ds_qual[ds->qual[ro + i]] += 1;
+                m->n[3] += ds->seq[ro + i] == 'N';
+            }
+            columns(1, j == 1, ds->d + ro, ds->e + ro, N);
+        }
     }
     return DCR_IO_OK;
 }

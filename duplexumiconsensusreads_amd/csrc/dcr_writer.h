@@ -36,6 +36,17 @@ struct FilterArgs {
     dcr_filter flt;
 };
 
+// the consensus QC tables (k_metrics, dcr_set_metrics)
+struct MetricsArgs {
+    dcr_out ss, ds;                 // device kernel outputs, read only (before k_filter masks ds)
+    const int32_t *sub_off;         // [4F+1]
+    const int64_t *ss_col_off, *ds_col_off;
+    const int32_t *fam_fail;        // [F] from k_famfail
+    int32_t n_fam;
+    dcr_metrics *out;               // the slot's accumulator, zeroed before the launch
+};
+constexpr int kMetThreads = 1024;   // k_metrics' workgroup: 16 waves on one set of LDS tables
+
 // the single-strand records' writer (k_fmt_size_ss / k_fmt_write_ss)
 struct FmtSsArgs {
     dcr_out ss;                     // device kernel outputs
@@ -76,6 +87,7 @@ struct CompactArgs {
 
 __global__ void k_famfail(FmtArgs A);
 __global__ void k_filter(FilterArgs A);
+__global__ void k_metrics(MetricsArgs A);
 __global__ void k_fmt_size(FmtArgs A);
 __global__ void k_fmt_write(FmtArgs A);
 __global__ void k_fmt_size_ss(FmtSsArgs A);

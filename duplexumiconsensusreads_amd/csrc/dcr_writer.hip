@@ -344,6 +344,255 @@ __global__ __launch_bounds__(256) void k_filter(FilterArgs A) {
     }
 }
 
+// ---- the consensus QC tables (dcr_set_metrics; include/dcr.h states them).
+// A workgroup of 16 waves, one wave per family at a time: first the four
+// single-strand records of its families, then the two duplex ones.
+// Nothing per base or per column goes to HBM one by one: a same-address
+// device atomic costs about 30 ns serialised and a batch holds ten million
+// columns in a few hundred bins.  Three levels instead:
+//   lanes   a lane takes 16 quality bytes (one dwordx4) and adds once per
+//           run of equal bytes; it takes 8 columns of d / e (one dwordx4) and
+//           keeps bins 8*lane .. 8*lane + 7 of the column tables in registers
+//           (column c' < 512 of every record belongs to the same lane);
+//   wave    the lanes whose 16 bytes all equal the first lane's quality (the
+//           hot bin) are added by one lane with one LDS add;
+//   LDS     the workgroup's copy of the whole dcr_metrics, 64-bit for the
+//           per-base tables and 32-bit for the per-record ones; at the end
+//           one global 64-bit add per non-zero bin per workgroup.
+// No counter wraps: the 32-bit register bins take at most 4 records * 65535
+// per family and are emptied into 64-bit LDS bins every kMetFlush families
+// (4 * 4096 * 65535 < 2^32); columns and record counts past bin 511, which
+// have no such bound, are summed in 64-bit lane variables; the 32-bit LDS
+// bins are per-record tables, each taking at most 2 per family of a batch
+// whose n_fam is an int32; everything else in LDS and HBM is 64-bit.
+// Loads: regions start on 16-column boundaries and are whole multiples of 16
+// columns, so a 16-byte load of qual / seq (16 columns) or of d / e (8
+// columns) that begins inside [0, n) on its own alignment stays inside the
+// region.  Reverse records are read from their end, 16 bytes at a 2-byte
+// alignment, so that column c' = n - 1 - c lands on the same lane as a
+// forward record's; a lane with fewer than 8 columns left reads them singly.
+// The single-strand seq is not touched.
+constexpr int kMetFlush = 4096;
+constexpr int kMetRecBase = (int)(offsetof(dcr_metrics, ss_reads) / 8);    // the per-record tables: 32-bit in LDS
+constexpr int kMetBigBase = (int)(offsetof(dcr_metrics, ss_qual) / 8);     // per base / per column: 64-bit in LDS
+constexpr int kMetWords = (int)(sizeof(dcr_metrics) / 8);
+constexpr int kMetDepth = (int)(offsetof(dcr_metrics, ds_depth) / 8) - kMetRecBase;
+constexpr int kMetErrC = (int)(offsetof(dcr_metrics, err_c) / 8) - kMetRecBase;
+constexpr int kMetErrS = (int)(offsetof(dcr_metrics, err_s) / 8) - kMetRecBase;
+constexpr int kMetCol = (int)(offsetof(dcr_metrics, col) / 8) - kMetBigBase;
+static_assert(sizeof(dcr_metrics) % 8 == 0 && offsetof(dcr_metrics, n) == 0 && kMetRecBase == 8 &&
+                  offsetof(dcr_metrics, ds_qual) / 8 - kMetBigBase == DCR_MET_QUAL_BINS && DCR_MET_COL_BINS == 8 * kW,
+              "k_metrics' LDS layout follows dcr_metrics");
+
+struct MetShared {
+    unsigned long long n[8];
+    unsigned long long big[kMetWords - kMetBigBase];    // ss_qual, ds_qual, col
+    uint32_t rec[kMetBigBase - kMetRecBase];            // ss_reads, ds_depth, err_c, err_s
+};
+
+// a lane's share of one kind's column tables: bins 8 * lane + t, and what falls past bin 511
+struct MetCols {
+    uint32_t cnt[8], d[8], e[8];
+    unsigned long long tail_n, tail_d, tail_e;
+};
+
+__device__ __forceinline__ int met_err_bin(double E) {
+    return (E >= 0.0 && E <= 1.0) ? (int)__builtin_rint(E * 1000.0) : DCR_MET_ERR_BINS - 1;
+}
+
+__device__ __forceinline__ int64_t met_clamp(int64_t v, int64_t hi) { return v < 0 ? 0 : v > hi ? hi : v; }
+
+// the quality bytes [0, L) of a region into the 256-bin histogram h (LDS)
+__device__ void met_qual(const uint8_t *q, uint32_t L, unsigned long long *h) {
+    for (uint32_t w = lane_id(); w < (L + 15) / 16; w += kW) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(q + 16 * w);
+        const int nb = L - 16 * w < 16 ? (int)(L - 16 * w) : 16;
+        const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+        uint32_t cur = x[0] & 0xffu, run = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t b = (x[i >> 2] >> (8 * (i & 3))) & 0xffu;
+            if (i < nb) {
+                if (b != cur) {
+                    atomicAdd(&h[cur], (unsigned long long)run);
+                    cur = b;
+                    run = 0;
+                }
+                ++run;
+            }
+        }
+        // the lanes still in the loop whose 16 bytes are all the first such lane's quality: one add
+        const uint32_t q0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur);
+        const bool hot = cur == q0 && run == 16;
+        const unsigned long long m = __ballot(hot);
+        if (!hot)
+            atomicAdd(&h[cur], (unsigned long long)run);
+        else if (lane_id() == (int)__builtin_ctzll(m))
+            atomicAdd(&h[q0], 16ull * (unsigned long long)__builtin_popcountll(m));
+    }
+}
+
+// this lane's count of 'N' among the bytes [0, L) of a region (at most L / 64 + 16: 32 bits hold it)
+__device__ uint32_t met_count_n(const uint8_t *s, uint32_t L) {
+    uint32_t n = 0;
+    for (uint32_t w = lane_id(); w < (L + 15) / 16; w += kW) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(s + 16 * w);
+        const int nb = L - 16 * w < 16 ? (int)(L - 16 * w) : 16;
+        const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) n += (i < nb && ((x[i >> 2] >> (8 * (i & 3))) & 0xffu) == 'N') ? 1u : 0u;
+    }
+    return n;
+}
+
+// v[t] = p[c'] for this lane's columns c' = c0 + t, t < nv (0 past them), of a
+// record of n columns; REV: c' counts from the record's end
+template <bool REV>
+__device__ __forceinline__ void met_load8(const uint16_t *p, uint32_t n, uint32_t c0, int nv, uint32_t v[8]) {
+    if (!REV) {
+        const uint4 r = *reinterpret_cast<const uint4 *>(p + c0);
+        const uint32_t x[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+        for (int t = 0; t < 8; ++t) v[t] = t < nv ? (x[t >> 1] >> (16 * (t & 1))) & 0xffffu : 0u;
+    } else if (nv >= 8) {
+        uint4 r;
+        __builtin_memcpy(&r, p + (n - 8 - c0), 16);
+        const uint32_t x[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+        for (int t = 0; t < 8; ++t) v[t] = (x[(7 - t) >> 1] >> (16 * ((7 - t) & 1))) & 0xffffu;
+    } else {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) v[t] = t < nv ? (uint32_t)p[n - 1 - c0 - t] : 0u;
+    }
+}
+
+template <bool REV>
+__device__ void met_cols(const uint16_t *d, const uint16_t *e, uint32_t n, MetCols &a) {
+    const uint32_t l8 = 8 * lane_id();
+#pragma unroll
+    for (int t = 0; t < 8; ++t) a.cnt[t] += l8 + t < n ? 1u : 0u;
+    if (n > DCR_MET_COL_BINS) a.tail_n += (unsigned long long)(n - DCR_MET_COL_BINS);
+    for (uint32_t base = 0; base < n; base += DCR_MET_COL_BINS) {      // n < 2^31: no wrap
+        const uint32_t c0 = base + l8;
+        if (c0 >= n) break;
+        const int nv = n - c0 < 8 ? (int)(n - c0) : 8;
+        uint32_t vd[8], ve[8];
+        met_load8<REV>(d, n, c0, nv, vd);
+        met_load8<REV>(e, n, c0, nv, ve);
+        if (base == 0) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                a.d[t] += vd[t];
+                a.e[t] += ve[t];
+            }
+        } else {
+            uint32_t sd = 0, se = 0;            // 8 * 65535 each
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                sd += vd[t];
+                se += ve[t];
+            }
+            a.tail_d += sd;
+            a.tail_e += se;
+        }
+    }
+}
+
+// a wave's register bins of one kind into the workgroup's tables, and cleared
+__device__ void met_flush(MetCols &a, unsigned long long *col) {
+    const int l8 = 8 * lane_id();
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        if (a.cnt[t]) atomicAdd(&col[0 * DCR_MET_COL_BINS + l8 + t], (unsigned long long)a.cnt[t]);
+        if (a.d[t]) atomicAdd(&col[1 * DCR_MET_COL_BINS + l8 + t], (unsigned long long)a.d[t]);
+        if (a.e[t]) atomicAdd(&col[2 * DCR_MET_COL_BINS + l8 + t], (unsigned long long)a.e[t]);
+        a.cnt[t] = a.d[t] = a.e[t] = 0;
+    }
+    // tail_n is the same in every lane (the record's n), the sums are each lane's own
+    if (a.tail_n && lane_id() == 0) atomicAdd(&col[0 * DCR_MET_COL_BINS + DCR_MET_COL_BINS - 1], a.tail_n);
+    if (a.tail_d) atomicAdd(&col[1 * DCR_MET_COL_BINS + DCR_MET_COL_BINS - 1], a.tail_d);
+    if (a.tail_e) atomicAdd(&col[2 * DCR_MET_COL_BINS + DCR_MET_COL_BINS - 1], a.tail_e);
+    a.tail_n = a.tail_d = a.tail_e = 0;
+}
+
+// One kind's records (DS: the two duplex ones, else the four single-strand
+// ones) of this wave's families.  Two passes over the families, one kind
+// each, keep one MetCols in registers at a time.
+template <bool DS>
+__device__ void met_pass(const MetricsArgs &A, MetShared &S, int wave, int nw) {
+    constexpr int R = DS ? 2 : 4;
+    const dcr_out &o = DS ? A.ds : A.ss;
+    const int64_t *col_off = DS ? A.ds_col_off : A.ss_col_off;
+    unsigned long long *qual = S.big + (DS ? DCR_MET_QUAL_BINS : 0);
+    unsigned long long *col = S.big + kMetCol + (DS ? 3 * DCR_MET_COL_BINS : 0);
+    MetCols c{};
+    unsigned long long n_len = 0, n_de = 0, n_n = 0;
+    uint32_t fams = 0, since = 0;
+    for (int64_t f = wave; f < A.n_fam; f += nw) {
+        if (A.fam_fail[f] != 0) continue;
+        ++fams;
+#pragma nounroll
+        for (int i = 0; i < R; ++i) {
+            const int64_t r = R * f + i;
+            const int64_t ro = col_off[r], room = col_off[r + 1] - ro;
+            // len and n_de are int32: the clamped values fit 31 bits
+            const uint32_t L = (uint32_t)met_clamp(o.len[r], room), N = (uint32_t)met_clamp(o.n_de[r], room);
+            n_len += L;
+            n_de += N;
+            if (lane_id() == 0) {
+                if (!DS) {
+                    const int64_t nr = met_clamp((int64_t)A.sub_off[r + 1] - A.sub_off[r], DCR_MET_READS_BINS - 1);
+                    atomicAdd(&S.rec[i * DCR_MET_READS_BINS + nr], 1u);
+                } else {
+                    const int64_t a = 4 * f + 2 * i, b = a + 1;
+                    const int aD = (int)met_clamp(A.ss.D[a], DCR_MET_DEPTH_BINS - 1);
+                    const int bD = (int)met_clamp(A.ss.D[b], DCR_MET_DEPTH_BINS - 1);
+                    const int hi = aD > bD ? aD : bD, lo = aD > bD ? bD : aD;
+                    atomicAdd(&S.rec[kMetDepth + hi * DCR_MET_DEPTH_BINS + lo], 1u);
+                    atomicAdd(&S.rec[kMetErrC + met_err_bin(A.ds.E[r])], 1u);
+                    const int ea = met_err_bin(A.ss.E[a]), eb = met_err_bin(A.ss.E[b]);
+                    atomicAdd(&S.rec[kMetErrS + (ea > eb ? ea : eb)], 1u);
+                }
+            }
+            met_qual(o.qual + ro, L, qual);
+            if (DS) n_n += met_count_n(o.seq + ro, L);
+            if (DS ? i == 0 : i < 2)
+                met_cols<false>(o.d + ro, o.e + ro, N, c);
+            else
+                met_cols<true>(o.d + ro, o.e + ro, N, c);
+        }
+        if (++since == kMetFlush) {
+            met_flush(c, col);
+            since = 0;
+        }
+    }
+    met_flush(c, col);
+    if (n_n) atomicAdd(&S.n[3], n_n);                         // each lane's own count
+    if (lane_id() == 0 && fams) {                             // the same in every lane
+        if (DS) atomicAdd(&S.n[0], (unsigned long long)fams);
+        atomicAdd(&S.n[DS ? 2 : 1], n_len);
+        atomicAdd(&S.n[DS ? 5 : 4], n_de);
+    }
+}
+
+__global__ __launch_bounds__(kMetThreads) void k_metrics(MetricsArgs A) {
+    __shared__ MetShared S;
+    for (int i = threadIdx.x; i < (int)(sizeof(MetShared) / 4); i += kMetThreads) reinterpret_cast<uint32_t *>(&S)[i] = 0;
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * kMetThreads + threadIdx.x) / kW));
+    const int nw = (int)(gridDim.x * (kMetThreads / kW));
+    met_pass<false>(A, S, wave, nw);
+    met_pass<true>(A, S, wave, nw);
+    __syncthreads();
+    // the workgroup's tables into the slot's: one 64-bit add per non-zero bin
+    unsigned long long *out = reinterpret_cast<unsigned long long *>(A.out);
+    for (int i = threadIdx.x; i < kMetWords; i += kMetThreads) {
+        const unsigned long long v =
+            i < kMetRecBase ? S.n[i] : i < kMetBigBase ? S.rec[i - kMetRecBase] : S.big[i - kMetBigBase];
+        if (v) atomicAdd(&out[i], v);
+    }
+}
+
 // one wave per duplex record; records of failing or dropped families get size 0
 __global__ __launch_bounds__(256) void k_fmt_size(FmtArgs A) {
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;

@@ -104,6 +104,7 @@ def load():
             "dcr_fmt_write": (_i32, [_vp, _vp, _vp, _vp, _i32]),
             "dcr_fmt_write_ss": (_i32, [_vp, _vp, _vp, _i32]),
             "dcr_fmt_filter": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
+            "dcr_fmt_metrics": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
             "dcr_fmt_write_filt": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
             "dcr_fmt_write_ss_filt": (_i32, [_vp, _vp, _vp, _i32, _vp]),
             "dcr_synth_write": (_i32, [_vp, _vp, _i32]),
@@ -444,6 +445,21 @@ def apply_filter(hb: HostBatch, ss: FmtOut, ds: FmtOut, flt, n_fam: int) -> np.n
                              out.ctypes.data) != 0:
         raise _err("consensus filter")
     return out[:n_fam]
+
+
+def metrics(hb: HostBatch, ss: FmtOut, ds: FmtOut, n_fam: int, fam_fail=None) -> np.ndarray:
+    """dcr_fmt_metrics: the consensus QC tables (include/dcr.h dcr_metrics) of
+    processed families [0, n_fam) as a uint64 block (params.metrics_fields
+    names its tables); with ``fam_fail`` (int32 per family) the families whose
+    word is not 0 are skipped.  To be called before ``apply_filter``, which
+    masks the duplex arrays in place."""
+    from .params import MET_WORDS
+    out = np.zeros(MET_WORDS, np.uint64)
+    ff = None if fam_fail is None else np.ascontiguousarray(fam_fail, np.int32)
+    if load().dcr_fmt_metrics(ctypes.byref(hb.s), ctypes.byref(ss), ctypes.byref(ds), n_fam,
+                              ff.ctypes.data if ff is not None else None, out.ctypes.data) != 0:
+        raise _err("consensus metrics")
+    return out
 
 
 def deflate_emulate(data: bytes) -> bytes:

@@ -21,6 +21,8 @@ import dataclasses
 import math
 import struct
 
+import numpy as np
+
 LUT_PLUS, LUT_DEL, LUT_N = 256, 257, 258
 MAX_QTHRESH = 257
 
@@ -173,6 +175,70 @@ class DcrFilter(ctypes.Structure):
                 ("min_reads", ctypes.c_int32 * 3), ("reserved0", ctypes.c_int32),
                 ("max_error_rate", ctypes.c_double * 2), ("max_no_call_fraction", ctypes.c_double),
                 ("min_mean_base_quality", ctypes.c_double)]
+
+
+# ---- consensus QC tables (include/dcr.h dcr_metrics; --metrics_output) ----------
+MET_READS_BINS, MET_DEPTH_BINS, MET_ERR_BINS, MET_QUAL_BINS, MET_COL_BINS = 256, 64, 1002, 256, 512
+
+
+class DcrMetrics(ctypes.Structure):
+    """Mirror of ``dcr_metrics`` (include/dcr.h): every field uint64."""
+    _fields_ = [("n", ctypes.c_uint64 * 8),
+                ("ss_reads", ctypes.c_uint64 * MET_READS_BINS * 4),
+                ("ds_depth", ctypes.c_uint64 * MET_DEPTH_BINS * MET_DEPTH_BINS),
+                ("err_c", ctypes.c_uint64 * MET_ERR_BINS), ("err_s", ctypes.c_uint64 * MET_ERR_BINS),
+                ("ss_qual", ctypes.c_uint64 * MET_QUAL_BINS), ("ds_qual", ctypes.c_uint64 * MET_QUAL_BINS),
+                ("col", ctypes.c_uint64 * MET_COL_BINS * 3 * 2)]
+
+
+MET_WORDS = ctypes.sizeof(DcrMetrics) // 8       # 10,716
+MET_N_NAMES = ("families", "ss_bases", "ds_bases", "ds_no_calls", "ss_columns", "ds_columns")
+
+
+def metrics_fields(words):
+    """The tables of a ``uint64[MET_WORDS]`` block as a dict of array views,
+    shaped as the struct's fields."""
+    words = np.asarray(words).reshape(-1)
+    if len(words) != MET_WORDS:
+        raise ValueError("not a dcr_metrics block")
+    out = {}
+    for name, ct in DcrMetrics._fields_:
+        f = getattr(DcrMetrics, name)
+        shape, t = [], ct
+        while hasattr(t, "_length_"):
+            shape.append(t._length_)
+            t = t._type_
+        out[name] = words[f.offset // 8:(f.offset + f.size) // 8].reshape(shape)
+    return out
+
+
+def _trimmed(a):
+    """A dense list without its trailing zeros."""
+    nz = np.flatnonzero(a)
+    return [int(v) for v in a[:int(nz[-1]) + 1]] if len(nz) else []
+
+
+def metrics_json(words) -> str:
+    """The ``--metrics_output`` file of a counter block: sorted keys and fixed
+    separators, so the same counters always give the same bytes."""
+    import json
+    m = metrics_fields(words)
+    doc = {"version": 1,
+           "bins": {"ss_reads_max": MET_READS_BINS - 1, "ds_depth_max": MET_DEPTH_BINS - 1,
+                    "column_max": MET_COL_BINS - 1, "error_rate_other": MET_ERR_BINS - 1}}
+    for i, name in enumerate(MET_N_NAMES):
+        doc[name] = int(m["n"][i])
+    doc["ss_reads"] = {k: _trimmed(m["ss_reads"][i]) for i, k in enumerate(("A1", "B2", "B1", "A2"))}
+    doc["ss_qual"], doc["ds_qual"] = _trimmed(m["ss_qual"]), _trimmed(m["ds_qual"])
+    doc["ds_depth"] = [[int(h), int(lo), int(m["ds_depth"][h, lo])] for h, lo in zip(*np.nonzero(m["ds_depth"]))]
+    for k in ("err_c", "err_s"):
+        doc[k] = [[int(b), int(m[k][b])] for b in np.flatnonzero(m[k])]
+    doc["col"] = {}
+    for i, kind in enumerate(("ss", "ds")):
+        rec = _trimmed(m["col"][i, 0])
+        doc["col"][kind] = {"records": rec, "depth": [int(v) for v in m["col"][i, 1, :len(rec)]],
+                            "errors": [int(v) for v in m["col"][i, 2, :len(rec)]]}
+    return json.dumps(doc, sort_keys=True, separators=(",", ":")) + "\n"
 
 
 def _numbers(text, conv, most, what):

@@ -131,8 +131,9 @@ class _WriterOut:
         self.blocks = None
 
         self.filt = None                 # pinned fam_filt, made when a filter is first set
+        self.met = None                  # pinned dcr_metrics, made when metrics are first on
 
-    def ensure(self, n_fam, bgzf_bytes, filt=False):
+    def ensure(self, n_fam, bgzf_bytes, filt=False, met=False):
         if n_fam > self.cap_f or self.small is None:
             self.cap_f = int(n_fam * 1.25) + 64
             self.small = Pinned(self.lib, 12 * self.cap_f + 64)
@@ -143,6 +144,10 @@ class _WriterOut:
         if filt and (self.filt is None or self.filt.nbytes < 4 * self.cap_f):
             self.filt = Pinned(self.lib, 4 * self.cap_f)
             self.fam_filt = self.filt.array.view(np.int32)
+        if met and self.met is None:
+            from .params import MET_WORDS
+            self.met = Pinned(self.lib, 8 * MET_WORDS)
+            self.metrics = self.met.array[:8 * MET_WORDS].view(np.uint64)
         if bgzf_bytes > self.cap_b:
             self.cap_b = int(bgzf_bytes * 1.25) + (1 << 20)
             self.blocks = Pinned(self.lib, self.cap_b)
@@ -161,12 +166,15 @@ class WriterResult:
     ``ss_bgzf`` / ``ss_record_bytes``: the blocks of those families' four
     single-strand records; None without it.  With a consensus filter set
     ``fam_filt``: the per-family outcome words (low byte not 0: dropped, its
-    records are not in the streams); None without one."""
+    records are not in the streams); None without one.  With ``metrics`` on,
+    ``metrics``: the batch's dcr_metrics as uint64 words (the slot's pinned
+    block, overwritten when the slot is submitted again); None without."""
 
-    def __init__(self, stream, slot, out, n_fam, out_ss=None, filtered=False):
+    def __init__(self, stream, slot, out, n_fam, out_ss=None, filtered=False, metrics=False):
         self._stream, self._slot = stream, slot
         self.fam_fail = out.fam_fail[:n_fam]
         self.fam_filt = out.fam_filt[:n_fam] if filtered else None
+        self.metrics = out.metrics if metrics else None
         self.ds_len = out.ds_len[:2 * n_fam]
         self.bgzf_bytes, self.record_bytes, self.blocks = (int(x) for x in out.totals[:3])
         self.bgzf = out.blocks.array[:self.bgzf_bytes]
@@ -206,7 +214,11 @@ class DeviceStream:
 
     ``filter`` (set per run too): a params.ConsensusFilter or None.  The
     device writer applies it (dcr_set_filter) and ``result`` carries
-    ``fam_filt``; on the host path the caller filters (native_io.apply_filter)."""
+    ``fam_filt``; on the host path the caller filters (native_io.apply_filter).
+
+    ``metrics`` (set per run too): the device writer counts the consensus QC
+    tables (dcr_set_metrics) and ``result`` carries them as ``metrics``; on the
+    host path the caller counts (native_io.metrics)."""
 
     def __init__(self, ctx, n_slots=2, owns_ctx=False, device_writer=True, persistent=False):
         """``persistent``: ``close`` only drains the slots (the context and the
@@ -221,6 +233,7 @@ class DeviceStream:
         self.device_writer = device_writer
         self.ss_output = False
         self.filter = None
+        self.metrics = False
         self.wouts_ss = None
         self.lib = _lib.load()
         self.n_slots = n_slots
@@ -254,9 +267,13 @@ class DeviceStream:
             wo = self.wouts[slot]
             # compressed records are far smaller than the kernel outputs; grown on demand
             filtered = self.filter is not None
-            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered)
-            # the context may serve other streams: its filter is this stream's for this batch
+            counted = bool(self.metrics)
+            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered, counted)
+            # the context may serve other streams: its filter and metrics are this stream's for this batch
             self.ctx.set_filter(self.filter)
+            self.ctx.set_metrics(counted)
+            if counted:
+                _lib._check(self.lib.dcr_slot_metrics_out(self.ctx._ctx, slot, wo.met.ptr))
             if filtered:
                 _lib._check(self.lib.dcr_slot_filter_out(self.ctx._ctx, slot, wo.filt.ptr))
             self._b = hb.batch_struct()
@@ -278,11 +295,11 @@ class DeviceStream:
                                                          ctypes.byref(ms), ctypes.byref(self._wres),
                                                          ctypes.byref(self._wres_ss)))
                 self.busy[slot] = True
-                return (slot, s.n_fam, True, filtered)
+                return (slot, s.n_fam, True, filtered, counted)
             _lib._check(self.lib.dcr_submit_write(self.ctx._ctx, slot, ctypes.byref(self._b), ctypes.byref(m),
                                                   ctypes.byref(self._wres)))
             self.busy[slot] = True
-            return (slot, s.n_fam, False, filtered)
+            return (slot, s.n_fam, False, filtered, counted)
         out = self.outs[slot]
         out.ensure(4 * s.n_fam, s.ss_cols, 2 * s.n_fam, s.ds_cols, s.n_reads,
                    SS_FIELDS_FULL if self.ss_output else SS_FIELDS)
@@ -317,7 +334,7 @@ class DeviceStream:
                     grown = True
             if not grown:
                 _lib._check(rc)
-            return WriterResult(self, slot, wo, n_fam, ws, handle[3])
+            return WriterResult(self, slot, wo, n_fam, ws, handle[3], handle[4])
         slot = handle
         _lib._check(self.lib.dcr_wait(self.ctx._ctx, slot))
         self.busy[slot] = False
@@ -345,7 +362,7 @@ class DeviceStream:
             if o.mem is not None:
                 o.mem.free()
         for w in self.wouts + (self.wouts_ss or []):
-            for m in (w.small, w.blocks, w.filt):
+            for m in (w.small, w.blocks, w.filt, w.met):
                 if m is not None:
                     m.free()
         if self.owns_ctx:
@@ -359,6 +376,7 @@ class CallBackend:
         self.fn, self.params = fn, params
         self.ss_output = False
         self.filter = None               # applied by the caller (native_io.apply_filter)
+        self.metrics = False             # counted by the caller (native_io.metrics)
         self._res = {}
         self._k = 0
 

@@ -284,6 +284,55 @@ int dcr_set_filter(dcr_ctx *ctx, const dcr_filter *filter);
  * when dcr_wait_write[_ss] returns.  NULL removes it. */
 int dcr_slot_filter_out(dcr_ctx *ctx, int slot, int32_t *fam_filt);
 
+/* Consensus QC tables (not a reference feature; what fgbio's
+ * CollectDuplexSeqMetrics / ErrorRateByReadPosition read off the written
+ * file).  With metrics on, dcr_submit_write[_ss] counts, over the families f
+ * of the batch with fam_fail[f] == 0 and before any filter masks or drops,
+ * the consensus as called.  Single-strand records s = 4f + k (k = A1 B2 B1
+ * A2), duplex records r = 2f + j built from a = 4f + 2j and b = a + 1.  len
+ * and n_de are clamped to [0, the record's region], as the filter clamps len.
+ *   n[0] families, [1] sum ss.len, [2] sum ds.len, [3] duplex bases == 'N',
+ *        [4] sum ss.n_de, [5] sum ds.n_de, [6] [7] 0
+ *   ss_reads[k][min(n, 255)]       n = sub_off[s+1] - sub_off[s]
+ *   ds_depth[min(hi, 63)][min(lo, 63)]  per duplex record: the larger and the
+ *        smaller of ss.D[a], ss.D[b], below 0 counted as 0
+ *   err_c[bin(ds.E[r])], err_s[max(bin(ss.E[a]), bin(ss.E[b]))]  per duplex
+ *        record; bin(E) = (int)rint(E * 1000.0) when E >= 0 && E <= 1, else
+ *        DCR_MET_ERR_BINS - 1 (NaN too); one double multiply
+ *   ss_qual[q], ds_qual[q]         every quality byte in [0, len)
+ *   col[kind][what][min(c', 511)]  kind 0 ss, 1 ds; what 0 records that have
+ *        the column, 1 sum of d, 2 sum of e; for every column c < n_de,
+ *        c' = c for forward records (ss k = 0, 1; ds j = 0) and
+ *        c' = n_de - 1 - c for reverse ones (ss k = 2, 3; ds j = 1): the
+ *        column counted from the read's sequencing 5' end
+ * Every table is an integer sum, so totals over batches or devices are sums
+ * of the blocks in any order. */
+#define DCR_MET_READS_BINS 256
+#define DCR_MET_DEPTH_BINS 64
+#define DCR_MET_ERR_BINS 1002
+#define DCR_MET_QUAL_BINS 256
+#define DCR_MET_COL_BINS 512
+typedef struct dcr_metrics {
+    uint64_t n[8];
+    uint64_t ss_reads[4][DCR_MET_READS_BINS];
+    uint64_t ds_depth[DCR_MET_DEPTH_BINS][DCR_MET_DEPTH_BINS];
+    uint64_t err_c[DCR_MET_ERR_BINS];
+    uint64_t err_s[DCR_MET_ERR_BINS];
+    uint64_t ss_qual[DCR_MET_QUAL_BINS];
+    uint64_t ds_qual[DCR_MET_QUAL_BINS];
+    uint64_t col[2][3][DCR_MET_COL_BINS];
+} dcr_metrics;
+/* on != 0: count (k_metrics, between the failure scan and the filter); 0: off
+ * (the default; nothing is launched, copied or allocated).  Holds for the
+ * batches submitted after the call. */
+int dcr_set_metrics(dcr_ctx *ctx, int on);
+/* Where a slot's counters go (pinned host memory, one dcr_metrics, written
+ * whole for every batch submitted on the slot while metrics are on: the
+ * batch's own counts, not a running total): copied with fam_fail, on the same
+ * stream and before the same event, so it is complete when
+ * dcr_wait_write[_ss] returns.  NULL removes it. */
+int dcr_slot_metrics_out(dcr_ctx *ctx, int slot, dcr_metrics *pinned_dst);
+
 /* CPU restatement with the same contract (oracle/, test infrastructure):
    host pointers, single thread (or n_threads > 1) */
 int dcr_oracle_run(const dcr_params *params, const dcr_batch *in, dcr_out *ss, dcr_out *ds,

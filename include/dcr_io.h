@@ -275,6 +275,15 @@ int dcr_fmt_write_filt(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out 
 int dcr_fmt_write_ss_filt(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, int32_t n_fam,
                           const int32_t *fam_filt);
 
+/* The consensus QC tables on the host (include/dcr.h dcr_metrics states the
+ * definitions; the device's k_metrics gives the same words).  Adds the counts
+ * of processed families [0, n_fam) into *m (the caller zeroes it), skipping
+ * the families with fam_fail[f] != 0 when fam_fail is not NULL.  To be called
+ * before dcr_fmt_filter, which masks the duplex arrays in place. */
+struct dcr_metrics;
+int dcr_fmt_metrics(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds, int32_t n_fam,
+                    const int32_t *fam_fail, struct dcr_metrics *m);
+
 /* ---- the GPU BGZF block compressor (csrc/dcr_deflate.h) emulated lane by
  * lane on the host, for tests: one BGZF block of in[0, n) (n <= 0xff00) into
  * out (>= 64 KiB); returns its size or -1 */
