@@ -48,6 +48,7 @@ EXPORTS = {
                                       ctypes.c_void_p]),
     "dcr_set_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "dcr_slot_filter_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "dcr_set_base_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "dcr_set_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "dcr_slot_metrics_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     # include/dcr_inflate.h: BGZF inflate on the device
@@ -152,6 +153,9 @@ class Context:
             return
         s = flt.as_struct() if flt is not None else None
         _check(load().dcr_set_filter(self._ctx, ctypes.byref(s) if s is not None else None))
+        # its per-base rules (dcr_set_base_filter), set and cleared with it
+        b = flt.as_base_struct() if flt is not None else None
+        _check(load().dcr_set_base_filter(self._ctx, ctypes.byref(b) if b is not None else None))
         self.filter = flt
 
     def set_metrics(self, on):

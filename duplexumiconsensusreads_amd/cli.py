@@ -21,7 +21,11 @@ builds (``make_consensus_read(method="single_strand")`` :1564-1569) and drops.
 ``--filter_*`` (not reference flags either) mask weak duplex bases and drop
 families whose duplex records have too little support or too many
 disagreements (include/dcr.h ``dcr_filter``): the step that otherwise follows
-on the written file.  Off by default; without one nothing changes.
+on the written file.  ``--filter_min_base_reads``, ``--filter_max_base_error_rate``
+and ``--filter_require_strand_agreement`` mask single duplex bases by the
+raw-read support and the strand agreement at the base's own alignment column
+(``dcr_base_filter``; device writer only).  Off by default; without one
+nothing changes.
 
 ``--metrics_output FILE.json`` (not a reference flag) writes the consensus QC
 tables (include/dcr.h ``dcr_metrics``): family sizes, strand depths, error
@@ -112,6 +116,15 @@ def parse_args(argv):
     ap.add_argument("--filter_min_mean_base_quality", required=False, default=None, metavar="Q",
                     type=params_mod.filter_min_mean_base_quality,
                     help="keep a duplex read whose mean base quality after masking is at least Q")
+    # the per-base rules (include/dcr.h dcr_base_filter): by the support and agreement at the base's own column
+    ap.add_argument("--filter_min_base_reads", required=False, default=None, metavar="T[,A[,B]]",
+                    type=params_mod.filter_min_base_reads,
+                    help="mask a duplex base unless, at its column, aD + bD >= T, max(aD, bD) >= A, min(aD, bD) >= B")
+    ap.add_argument("--filter_max_base_error_rate", required=False, default=None, metavar="X",
+                    type=params_mod.filter_max_base_error_rate,
+                    help="mask a duplex base whose column has aE + bE > X * (aD + bD)")
+    ap.add_argument("--filter_require_strand_agreement", action="store_true",
+                    help="mask a duplex base where the two single-strand consensus reads disagree (cE > 0)")
     # not a reference flag: the consensus QC tables (include/dcr.h dcr_metrics) as JSON
     ap.add_argument("--metrics_output", required=False, default=None, type=str, metavar="FILE.json",
                     help="count family sizes, strand depths, error rates, qualities and errors by read position "
@@ -274,6 +287,9 @@ def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=Fa
         be.ss_output = ss_output
     elif ss_output:
         raise ValueError("this backend cannot produce the single-strand records")
+    if flt is not None and flt.base_active and not getattr(be, "device_writer", False):
+        # the column of a base is only known on the device (the kernels' maps)
+        raise ValueError("this backend cannot apply the per-base filters")
     if hasattr(be, "filter"):
         be.filter = flt
     elif flt is not None:

@@ -219,6 +219,10 @@ struct WriterBufs {
     uint32_t *tok;
     int32_t *fam_filt;      // k_filter's outcomes; null unless a filter is set (dcr_set_filter)
     dcr_metrics *metrics;   // k_metrics' accumulator; null unless metrics are on (dcr_set_metrics)
+    // null unless a base filter is set (dcr_set_base_filter): k_base_filter's count per family and
+    // the column maps k_consensus_general stores for it
+    int32_t *base_masked;
+    dcr::BaseMap bmap;
 };
 
 // The second stream of dcr_submit_write_ss: the single-strand records'
@@ -237,13 +241,33 @@ struct WriterSsBufs {
     uint32_t *tok;
 };
 
+// the single-strand stream's regions (plan_writer)
+void plan_writer_ss(int64_t F, Plan &p, WriterSsBufs &ws) {
+    ws.sub_flag = p.take<uint16_t>(4 * (size_t)F);
+    ws.sub_mi = p.take<int64_t>(4 * (size_t)F);
+    ws.sub_rx = p.take<int64_t>(4 * (size_t)F);
+    ws.rec_size = p.take<int64_t>((size_t)(4 * F + 1));
+    ws.rec_off = p.take<int64_t>((size_t)(4 * F + 1));
+    ws.scan = (int64_t *)p.take<char>(
+        std::max(dcrw::scan_tmp_bytes((int)(4 * F + 1)), dcrw::scan_tmp_bytes((int)(ws.nbm + 1))));
+    ws.stream = p.take<uint8_t>((size_t)ws.B);
+    ws.slots = p.take<uint8_t>((size_t)ws.nbm * dfl::kSlot);
+    ws.bsz = p.take<int64_t>((size_t)(ws.nbm + 2));
+    ws.boff = p.take<int64_t>((size_t)(ws.nbm + 1));
+    ws.comp = p.take<uint8_t>((size_t)ws.nbm * dfl::kSlot);
+    ws.tot = p.take<int64_t>(4);
+    ws.tok = p.take<uint32_t>((size_t)ws.gd * dfl::kTokWords);
+}
+
 // F families, n_names bytes of names, a record stream of at most B bytes in
 // at most nbm blocks, gd k_deflate workgroups; with ws, the single-strand
 // stream's regions after them (the first stream's layout does not change)
 // and with filt, k_filter's outcomes (no region without it); with met,
-// k_metrics' accumulator (none without it)
+// k_metrics' accumulator (none without it); with bf (the batch, when a base
+// filter is set), k_base_filter's counts and the column maps, after every
+// other region (none without it)
 void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w,
-                 WriterSsBufs *ws = nullptr, bool filt = false, bool met = false) {
+                 WriterSsBufs *ws = nullptr, bool filt = false, bool met = false, const dcr_batch *bf = nullptr) {
     w.names = p.take<char>((size_t)n_names + 1);
     w.fam_code = p.take<int64_t>((size_t)F);
     w.fam_rx = p.take<int64_t>(2 * (size_t)F);
@@ -262,21 +286,16 @@ void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd
     w.tok = p.take<uint32_t>((size_t)gd * dfl::kTokWords);
     w.fam_filt = filt ? p.take<int32_t>((size_t)F) : nullptr;
     w.metrics = met ? p.take<dcr_metrics>(1) : nullptr;
-    if (!ws) return;
-    ws->sub_flag = p.take<uint16_t>(4 * (size_t)F);
-    ws->sub_mi = p.take<int64_t>(4 * (size_t)F);
-    ws->sub_rx = p.take<int64_t>(4 * (size_t)F);
-    ws->rec_size = p.take<int64_t>((size_t)(4 * F + 1));
-    ws->rec_off = p.take<int64_t>((size_t)(4 * F + 1));
-    ws->scan = (int64_t *)p.take<char>(
-        std::max(dcrw::scan_tmp_bytes((int)(4 * F + 1)), dcrw::scan_tmp_bytes((int)(ws->nbm + 1))));
-    ws->stream = p.take<uint8_t>((size_t)ws->B);
-    ws->slots = p.take<uint8_t>((size_t)ws->nbm * dfl::kSlot);
-    ws->bsz = p.take<int64_t>((size_t)(ws->nbm + 2));
-    ws->boff = p.take<int64_t>((size_t)(ws->nbm + 1));
-    ws->comp = p.take<uint8_t>((size_t)ws->nbm * dfl::kSlot);
-    ws->tot = p.take<int64_t>(4);
-    ws->tok = p.take<uint32_t>((size_t)ws->gd * dfl::kTokWords);
+    if (ws) plan_writer_ss(F, p, *ws);
+    w.base_masked = nullptr;
+    w.bmap = dcr::BaseMap{};
+    if (bf) {
+        w.base_masked = p.take<int32_t>((size_t)F);
+        w.bmap.flag = p.take<uint8_t>(6 * (size_t)F);
+        w.bmap.ss_col = p.take<uint32_t>((size_t)bf->ss_cols);
+        w.bmap.ds_col = p.take<uint32_t>((size_t)bf->ds_cols);
+        w.bmap.ds_aln = p.take<uint32_t>((size_t)bf->ds_cols);
+    }
 }
 }  // namespace
 
@@ -315,6 +334,7 @@ struct dcr_ctx {
         // the single-strand stream of dcr_submit_write_ss (writer_ss)
         int64_t *d_ss_rec_off = nullptr;
         uint8_t *d_ss_stream = nullptr, *d_ss_comp = nullptr;
+        uint8_t *d_map_flag = nullptr;   // the batch's BaseMap::flag when a base filter was set, else null
         int64_t n_fam = 0;
         bool writer = false, writer_ss = false;
         hipEvent_t ev_h2d = nullptr, ev_comp = nullptr, ev_d2h = nullptr;
@@ -332,6 +352,10 @@ struct dcr_ctx {
     dcr_params host_params{};
     dcr_filter filter{};    // dcr_set_filter; active == 0: off
     bool metrics = false;   // dcr_set_metrics
+    dcr_base_filter base_filter{};   // dcr_set_base_filter; active == 0: off
+    // the column maps of the batch being submitted (submit_write sets them around its
+    // dcr_run_batch when a base filter is set); all null otherwise
+    dcr::BaseMap bmap{};
     // fast-kernel constants (fast_constants)
     uint32_t fast_kq = 0, fast_kqlo = 0;
     int fast_maxq = 0, fast_t16 = 0, fast_r_safe = 0, fast_qlo = 0;
@@ -584,7 +608,11 @@ static int launch_strand(dcr_ctx *c, dcr::Args &a, const dcr_batch *in, const dc
     // after k_decide_deep: it reads the general list's entries, which
     // k_ins_layout marks decided (bit 31) for the records it decides
     hipLaunchKernelGGL(dcr::k_ins_layout<DUPLEX>, dim3(grid_for(2048)), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(dcr::k_consensus_general<DUPLEX>, dim3(grid_for(1024)), dim3(256), 0, c->stream, a);
+    // with a base filter set, the instantiation that also stores the base maps
+    if (c->bmap.flag)
+        hipLaunchKernelGGL(dcr::k_consensus_general_map<DUPLEX>, dim3(grid_for(1024)), dim3(256), 0, c->stream, a, c->bmap);
+    else
+        hipLaunchKernelGGL(dcr::k_consensus_general<DUPLEX>, dim3(grid_for(1024)), dim3(256), 0, c->stream, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[3], c->stream));
     return DCR_OK;
@@ -1007,17 +1035,19 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         wsb.nbm = wsb.B / (int64_t)dfl::kMaxIn + 2;
         wsb.gd = (unsigned)std::max<int64_t>(1, std::min<int64_t>(wsb.nbm, (int64_t)c->n_cu * c->dfl_blocks));
     }
-    const bool filt = c->filter.active != 0;
+    // a base filter alone still gives fam_filt: k_filter runs to add the masked counts into it
+    const bool bfilt = c->base_filter.active != 0;
+    const bool filt = c->filter.active != 0 || bfilt;
     if (filt && F && !S.h_fam_filt)
         return fail(DCR_EARG, "a filter is set but the slot has no fam_filt destination (dcr_slot_filter_out)");
     const bool met = c->metrics;
     if (met && !S.h_metrics)
         return fail(DCR_EARG, "metrics are on but the slot has no destination (dcr_slot_metrics_out)");
     Plan wsz;
-    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met);
+    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met, bfilt ? h : nullptr);
     if (wsz.off > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wsz.off + wsz.off / 8));
     Plan wp{(char *)S.wbuf.p};
-    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met);
+    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met, bfilt ? h : nullptr);
     // H2D: inputs and writer metadata on the copy stream
     HIP_TRY(upload_inputs(h, db, c->s_h2d));
     if (m->n_names) HIP_TRY(hipMemcpyAsync(wb.names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
@@ -1031,7 +1061,13 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         HIP_TRY(hipMemcpyAsync(wsb.sub_mi, ms->sub_mi, 32 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
         HIP_TRY(hipMemcpyAsync(wsb.sub_rx, ms->sub_rx, 32 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
     }
-    if ((rc = slot_run(c, S, h, &db, dout))) return rc;
+    // with a base filter the general kernels store the column maps of the records with
+    // insertion columns and flag them; the flags start from zero for every batch
+    if (bfilt && F) HIP_TRY(hipMemsetAsync(wb.bmap.flag, 0, 6 * (size_t)F, c->stream));
+    c->bmap = wb.bmap;
+    rc = slot_run(c, S, h, &db, dout);
+    c->bmap = dcr::BaseMap{};
+    if (rc) return rc;
     // record writer
     dcrw::FmtArgs A{};
     A.ss = dout[0];
@@ -1069,8 +1105,20 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         }
         if (filt) {
             // one wave per family, before anything reads the duplex seq / qual
-            dcrw::FilterArgs Fa{dout[0], dout[1], db.ds_col_off, wb.fam_fail, wb.fam_filt, (int32_t)F, c->filter};
             const unsigned gf = (unsigned)std::max<int64_t>(1, std::min<int64_t>((F + 3) / 4, (int64_t)c->n_cu * 8));
+            if (bfilt) {
+                // after k_metrics (the tables describe the consensus as called), before k_filter
+                // (its record rules see the bases masked here); the bases k_filter's own
+                // quality rule masks are left to it, so every masked base is counted once
+                const bool mq = (c->filter.active & DCR_FILT_MASK_BASES) != 0;
+                dcrw::BaseFilterArgs Ba{dout[0], dout[1], db.sub_off, db.read_pos, db.ss_col_off, db.ds_col_off,
+                                        wb.fam_fail, wb.bmap.ss_col, wb.bmap.ds_col, wb.bmap.ds_aln, wb.bmap.flag,
+                                        wb.base_masked, (int32_t)F,
+                                        mq ? std::min<int32_t>(c->filter.min_base_quality, 256) : 0, c->base_filter};
+                hipLaunchKernelGGL(dcrw::k_base_filter, dim3(gf), dim3(256), 0, c->stream, Ba);
+            }
+            dcrw::FilterArgs Fa{dout[0], dout[1], db.ds_col_off, wb.fam_fail, wb.fam_filt, (int32_t)F, c->filter,
+                                wb.base_masked};
             hipLaunchKernelGGL(dcrw::k_filter, dim3(gf), dim3(256), 0, c->stream, Fa);
         }
         const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((2 * F + 3) / 4, (int64_t)c->n_cu * 8));
@@ -1149,6 +1197,7 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     S.d_ss_rec_off = ms ? wsb.rec_off : nullptr;
     S.d_ss_stream = ms ? wsb.stream : nullptr;
     S.d_ss_comp = ms ? wsb.comp : nullptr;
+    S.d_map_flag = wb.bmap.flag;
     S.n_fam = F;
     S.writer = true;
     S.writer_ss = ms != nullptr;
@@ -1175,6 +1224,22 @@ int dcr_set_filter(dcr_ctx *c, const dcr_filter *f) {
     if ((f->active & DCR_FILT_MEAN_QUAL) && !(f->min_mean_base_quality >= 0.0))
         return fail(DCR_EARG, "filter min_mean_base_quality < 0");
     c->filter = *f;
+    return DCR_OK;
+}
+
+int dcr_set_base_filter(dcr_ctx *c, const dcr_base_filter *f) {
+    if (!c) return fail(DCR_EARG, "NULL context");
+    if (!f || f->active == 0) {
+        c->base_filter = dcr_base_filter{};
+        return DCR_OK;
+    }
+    if (f->active & ~(DCR_BF_MIN_READS | DCR_BF_ERROR_RATE | DCR_BF_AGREEMENT))
+        return fail(DCR_EARG, "unknown base filter bits");
+    if ((f->active & DCR_BF_MIN_READS) && !(f->min_reads[0] >= f->min_reads[1] && f->min_reads[1] >= f->min_reads[2]))
+        return fail(DCR_EARG, "base filter min_reads must be total >= larger strand >= smaller strand");
+    if ((f->active & DCR_BF_ERROR_RATE) && !(f->max_error_rate >= 0.0 && f->max_error_rate <= 1.0))
+        return fail(DCR_EARG, "base filter max_error_rate outside [0, 1]");
+    c->base_filter = *f;
     return DCR_OK;
 }
 
@@ -1274,9 +1339,13 @@ int dcr_slot_fetch(dcr_ctx *c, int slot, int what, int64_t off, int64_t n, void 
         } else {
             if (n) HIP_TRY(hipMemcpy(dst, S.d_ss_comp + off, (size_t)n, hipMemcpyDeviceToHost));
         }
+    } else if (what == 6) {
+        if (!S.d_map_flag) return fail(DCR_EARG, "slot's batch ran without a base filter");
+        if (off + n > 6 * S.n_fam) return fail(DCR_EARG, "map flags out of range");
+        if (n) HIP_TRY(hipMemcpy(dst, S.d_map_flag + off, (size_t)n, hipMemcpyDeviceToHost));
     } else {
-        return fail(DCR_EARG, "what must be 0 (record bytes), 1 (record offsets), 2 (BGZF blocks) or 3 to 5 "
-                              "(the same of the single-strand stream)");
+        return fail(DCR_EARG, "what must be 0 (record bytes), 1 (record offsets), 2 (BGZF blocks), 3 to 5 "
+                              "(the same of the single-strand stream) or 6 (stored-map flags)");
     }
     return DCR_OK;
 }

@@ -83,6 +83,19 @@ struct Workspace {
 };
 constexpr int kLayRow = 256;        // columns per laid-out row (records of T <= 256)
 
+// The column of every kept base of the records that have insertion columns
+// (dcr_set_base_filter; include/dcr.h "Level 1"): their consensus CIGAR does
+// not say it (an insertion next to a deletion is one M over two columns, and
+// a '+' column is in no list), so k_consensus_general_map, which finalises
+// them when a base filter is set, stores it.  Every other record's map
+// follows from its pos and CIGAR.  Device regions of the slot's writer buffer.
+struct BaseMap {
+    uint8_t *flag;          // [6F] 1: the record's map is stored (single-strand 4F, then duplex 2F); zeroed per batch
+    uint32_t *ss_col;       // [ss cols] at ss_col_off[s] + i: the d-index of base i of single-strand record s
+    uint32_t *ds_col;       // [ds cols] the same for the duplex records
+    uint32_t *ds_aln;       // [ds cols] the alignment column of duplex base i, '+' columns counted
+};
+
 struct Args {
     dcr_batch in;
     const dcr_params *P;
@@ -143,6 +156,7 @@ __global__ void k_fast_rows(FastArgs a);
 __global__ void k_r2_table(const dcr_params *P, uint32_t *tab);
 constexpr int kR2Entries = 5 * 128 * 5 * 128;
 template <bool DUPLEX> __global__ void k_consensus_general(Args a);
+template <bool DUPLEX> __global__ void k_consensus_general_map(Args a, BaseMap bm);   // ... storing the base maps
 template <bool DUPLEX> __global__ void k_decide(Args a);
 template <bool DUPLEX> __global__ void k_ins_layout(Args a);
 __global__ void k_decide_deep(Args a);

@@ -1251,10 +1251,13 @@ struct GStamp {
 // One consensus record (single-strand subfamily or duplex pair) of the general
 // list on one wave (k_consensus_general): every layout, the staged one
 // included.
-template <bool DUPLEX>
+// MAP (k_consensus_general_map, launched instead when a base filter is set):
+// also store the column of every kept base of the records with insertion
+// columns into *bmp (BaseMap); without it nothing of that is compiled in.
+template <bool DUPLEX, bool MAP = false>
 __device__ __forceinline__ void process_record(const Args &a, const int64_t rec, WaveLds &W, const double2 *s_lut,
                                                const double *s_qthr, const uint32_t *s_wtab, const bool decided,
-                                               const int lane, GStamp &gs) {
+                                               const int lane, GStamp &gs, const BaseMap *bmp = nullptr) {
     const dcr_params *P = a.P;
     gs.start();
 
@@ -1803,6 +1806,14 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
     uint32_t *rstart_buf = cols_lds ? (uint32_t *)W.stage : ocig;
     int nruns = 0, nops = 0, nlen = 0, last_op = -1, chain_start = lo;
     bool kept_overflow = false;
+    // MAP: the column of every kept base, for the per-base filters (BaseMap):
+    // only records with insertion columns.  No '+' column lies before lo
+    // (the trimmed columns are 'N'), so the d-index of column t is t less
+    // the '+' columns of [lo, t)
+    const bool bm_on = MAP && ins;
+    const BaseMap bmap = MAP ? *bmp : BaseMap{};
+    uint32_t *bm_col = DUPLEX ? bmap.ds_col : bmap.ss_col;
+    int nplus = 0;
     for (int c0 = lo; c0 < hi; c0 += kWave) {
         const int t = c0 + lane;
         const bool live = t < hi;
@@ -1863,6 +1874,15 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
             oseq[si] = (uint8_t)(isL ? ch - 32 : ch);
             oqual[si] = (uint8_t)q;
             kept_overflow |= (q < 0 || q > 255);
+        }
+        if (bm_on) {
+            const uint64_t pm = __ballot(live && isP);
+            if (ks) {
+                const int si = nlen + __popcll(sm & lanemask_lt(lane));
+                bm_col[off + si] = (uint32_t)(t - nplus - __popcll(pm & lanemask_lt(lane)));
+                if (DUPLEX) bmap.ds_aln[off + si] = (uint32_t)t;
+            }
+            nplus += __popcll(pm);
         }
         nlen += __popcll(sm);
     }
@@ -1975,6 +1995,7 @@ __device__ __forceinline__ void process_record(const Args &a, const int64_t rec,
         O.D[rec] = Dmax;
         O.M[rec] = Dmin;
         O.E[rec] = E;
+        if (bm_on) bmap.flag[lrec] = 1;
     }
     gs.mark(7);
     gs.record(!ins ? 0 : laid ? (big ? 2 : 1) : !big ? 1 : regbig ? 2 : 3);
@@ -4044,6 +4065,45 @@ __global__ __launch_bounds__(kBlock, DCR_GEN_OCC) void k_consensus_general(Args 
         for (int k = 0; k < 20; ++k) atomicAdd(&a.ws.stamps[k + (DUPLEX ? 32 : 0)], (unsigned long long)gs.acc[k]);
 }
 
+// The same kernel storing the base maps into bm (process_record<., true>),
+// launched in its place for the batches of a context with a base filter set,
+// so that the default path runs the kernel it always ran.  The loop is
+// k_consensus_general's, word for word (written out twice: routed through a
+// shared device function the default kernel's instructions come out in
+// another order).
+template <bool DUPLEX>
+__global__ __launch_bounds__(kBlock, DCR_GEN_OCC) void k_consensus_general_map(Args a, BaseMap bm) {
+    __shared__ double2 s_lut[DCR_LUT_N];
+    __shared__ double s_qthr[DCR_MAX_QTHRESH];
+    __shared__ WaveLds s_wave[kWavesPerBlock];
+    __shared__ uint32_t s_wtab[DCR_LUT_N];
+    const dcr_params *P = a.P;
+    for (int i = threadIdx.x; i < DCR_LUT_N; i += kBlock) s_lut[i] = make_double2(P->match[i], P->mismatch[i]);
+    if (a.t16 >= 0)
+        for (int i = threadIdx.x; i < DCR_LUT_N; i += kBlock) s_wtab[i] = a.wtab[i];
+    for (int i = threadIdx.x; i < DCR_MAX_QTHRESH; i += kBlock) s_qthr[i] = P->qthresh[i];
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int n = a.ws.ovf_count[DUPLEX ? 1 : 0];
+    int *next = a.ws.gen_next + (DUPLEX ? 1 : 0);
+    const int nw = gridDim.x * kWavesPerBlock;
+    GStamp gs;
+    for (int i = blockIdx.x * kWavesPerBlock + wave;;) {
+        if (i >= n) break;
+        const int v = a.ws.ovf[i];
+        process_record<DUPLEX, true>(a, v & 0x7fffffff, s_wave[wave], s_lut, s_qthr, s_wtab, v < 0, lane, gs, &bm);
+        if (nw >= n) break;
+        const uint64_t act = __ballot(1);                 // the claim by the first active lane, as above
+        const int leader = __ffsll((long long)act) - 1;
+        int t = 0;
+        if (lane == leader) t = atomicAdd(next, 1);
+        i = nw + __builtin_amdgcn_readfirstlane(__shfl(t, leader, kWave));
+    }
+    if (DCR_GSTAMP && lane == 0)
+        for (int k = 0; k < 20; ++k) atomicAdd(&a.ws.stamps[k + (DUPLEX ? 32 : 0)], (unsigned long long)gs.acc[k]);
+}
+
 // Insertion layouts by events (see run_at): one wave per general-list record
 // with an insertion column, 4-wave blocks, few registers.  Writes the record's
 // block (insertion mask, then every read's row of element codes over the T
@@ -4531,5 +4591,7 @@ template __global__ void k_decide<true>(Args);
 template __global__ void k_ins_layout<false>(Args);
 template __global__ void k_ins_layout<true>(Args);
 template __global__ void k_consensus_general<true>(Args);
+template __global__ void k_consensus_general_map<false>(Args, BaseMap);
+template __global__ void k_consensus_general_map<true>(Args, BaseMap);
 
 }  // namespace dcr

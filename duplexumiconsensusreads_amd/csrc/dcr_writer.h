@@ -34,6 +34,24 @@ struct FilterArgs {
     int32_t *fam_filt;              // [F] reason bits | masked bases << 8
     int32_t n_fam;
     dcr_filter flt;
+    const int32_t *base_masked;     // [F] bases k_base_filter masked, added into fam_filt >> 8; or null
+};
+
+// the per-base filters (k_base_filter, dcr_set_base_filter)
+struct BaseFilterArgs {
+    dcr_out ss, ds;                 // device kernel outputs; ds.seq / ds.qual are masked in place
+    const int32_t *sub_off;         // [4F+1]
+    const int32_t *read_pos;        // [n_reads]
+    const int64_t *ss_col_off, *ds_col_off;
+    const int32_t *fam_fail;        // [F] from k_famfail
+    // the stored maps of the records with insertion columns (dcr::BaseMap)
+    const uint32_t *ss_col, *ds_col, *ds_aln;
+    const uint8_t *flag;            // [6F]
+    int32_t *masked;                // [F] bases masked here whose new quality min(q, 2) is not below skip_below:
+                                    // the others k_filter masks again and counts (0 for failing families)
+    int32_t n_fam;
+    int32_t skip_below;             // bases of a quality below this are left to k_filter, which masks and counts them
+    dcr_base_filter flt;
 };
 
 // the consensus QC tables (k_metrics, dcr_set_metrics)
@@ -87,6 +105,7 @@ struct CompactArgs {
 
 __global__ void k_famfail(FmtArgs A);
 __global__ void k_filter(FilterArgs A);
+__global__ void k_base_filter(BaseFilterArgs A);
 __global__ void k_metrics(MetricsArgs A);
 __global__ void k_fmt_size(FmtArgs A);
 __global__ void k_fmt_write(FmtArgs A);

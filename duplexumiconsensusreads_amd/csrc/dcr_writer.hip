@@ -340,7 +340,243 @@ __global__ __launch_bounds__(256) void k_filter(FilterArgs A) {
             if ((T.active & DCR_FILT_MEAN_QUAL) && (double)q_sum < T.min_mean_base_quality * (double)L)
                 why |= DCR_FILT_MEAN_QUAL;
         }
+        // k_base_filter's count leaves out every base whose quality it left below minq (those were
+        // counted above), so the sum counts each masked base once
+        if (A.base_masked) masked += (uint32_t)A.base_masked[f];
         if (lane_id() == 0) A.fam_filt[f] = (int32_t)(why | (masked << 8));
+    }
+}
+
+// ---- the per-base filters (dcr_set_base_filter; include/dcr.h states the
+// rules and the two levels of the map).  One wave per family, both duplex
+// records, the lanes striding seq / qual a dword at a time as k_filter does;
+// runs before k_filter, which then counts 'N' and sums qualities over the
+// bases masked here and adds this kernel's count into fam_filt.
+//
+// A lane finds the columns of its own bases; no LDS.  Records without
+// insertion columns (the fast list's single M runs, and whatever else has no
+// stored map) follow from pos and CIGAR: t5 = pos - min(read pos), an M run
+// is bases on consecutive columns, a D run skips columns.  When the duplex
+// record and both strands are one M run each this is lane arithmetic
+// (col_r(i) = t5_r + i, ia = min_pos_r + col_r(i) - pos_a, col_a(ia) = t5_a +
+// ia); otherwise each lane walks the few runs of the two strands' CIGARs the
+// way reconstruct_alignment (:430-547) lays them out, and reads the stored
+// maps (dcr::BaseMap) of the records that have them.  Every index is
+// clamped to the record's region before it is used.
+struct BfRec {
+    const uint32_t *cig;    // consensus CIGAR
+    const uint32_t *col;    // stored d-index per base (mapped), else unused
+    const uint16_t *d, *e;
+    int64_t len, nde, ncig; // clamped to [0, the region]
+    int64_t pos, t5;
+    bool mapped, simple;    // a stored map; one M run of len bases and no stored map
+};
+
+constexpr int64_t kBfInf = (int64_t)1 << 40;
+
+__device__ __forceinline__ int64_t bf_clamp(int64_t v, int64_t hi) { return v < 0 ? 0 : v > hi ? hi : v; }
+
+__device__ __forceinline__ void bf_rec(const dcr_out &o, const int64_t *col_off, int64_t r, const uint32_t *col,
+                                       bool mapped, BfRec &R) {
+    const int64_t ro = col_off[r], room = col_off[r + 1] - ro;
+    R.cig = o.cigar + ro;
+    R.col = col + ro;
+    R.d = o.d + ro;
+    R.e = o.e + ro;
+    R.len = bf_clamp(o.len[r], room);
+    R.nde = bf_clamp(o.n_de[r], room);
+    R.ncig = bf_clamp(o.n_cig[r], room);
+    R.pos = o.pos[r];
+    R.t5 = 0;
+    R.mapped = mapped;
+    R.simple = !mapped && R.ncig == 1 && R.len > 0 && R.cig[0] == ((uint32_t)R.len << 4);
+}
+
+// the d-index of base i of a record (Level 1), -1 when it has none
+__device__ int64_t bf_own_col(const BfRec &R, int64_t i) {
+    if (i < 0 || i >= R.len) return -1;
+    if (R.mapped) return (int64_t)R.col[i];
+    if (R.simple) return R.t5 + i;
+    int64_t is = 0, dc = R.t5;
+    for (int64_t k = 0; k < R.ncig; ++k) {
+        const int64_t n = R.cig[k] >> 4;
+        if ((R.cig[k] & 15u) == 2u) {
+            dc += n;
+        } else {
+            if (i < is + n) return dc + (i - is);
+            is += n;
+            dc += n;
+        }
+    }
+    return -1;
+}
+
+// a strand's place in its CIGAR during the two-read layout
+struct BfCur {
+    int64_t k, rem, is;
+    int op;                 // 0 base-consuming, 1 I, 2 D (:361-377: everything but I and D lays a base)
+};
+__device__ __forceinline__ void bf_load(const BfRec &R, BfCur &c) {
+    while (c.k < R.ncig && (R.cig[c.k] >> 4) == 0) ++c.k;     // expand_cigartuples drops empty runs
+    if (c.k < R.ncig) {
+        const uint32_t v = R.cig[c.k];
+        c.rem = v >> 4;
+        c.op = (v & 15u) == 1u ? 1 : (v & 15u) == 2u ? 2 : 0;
+    } else {
+        c.rem = kBfInf;     // past the last run: the reference reads M (:408-427)
+        c.op = 0;
+    }
+}
+
+// Level 2: the base indices ia / ib (-1: none) that the two strands put into
+// alignment column t of their duplex record, by runs instead of by columns
+__device__ void bf_sources(const BfRec &A, const BfRec &B, int64_t minpos, int64_t t, int64_t &ia, int64_t &ib) {
+    const BfRec *R[2] = {&A, &B};
+    BfCur c[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    bf_load(A, c[0]);
+    bf_load(B, c[1]);
+    int64_t out[2] = {-1, -1};
+    int64_t col = 0, p = minpos;
+    while (col <= t) {
+        int64_t n = kBfInf, src[2] = {-1, -1};
+        int kind[2] = {0, 0};                      // 0 nothing, 1 bases, 2 deletion, 3 inserted bases
+        if (c[0].op == 1 || c[1].op == 1) {        // insertion columns (:476-503): '+' for the other strand
+            for (int s = 0; s < 2; ++s)
+                if (c[s].op == 1) {
+                    kind[s] = 3;
+                    src[s] = c[s].is;
+                    n = c[s].rem < n ? c[s].rem : n;
+                }
+        } else {
+            for (int s = 0; s < 2; ++s) {
+                int64_t seg = kBfInf;
+                if (p < R[s]->pos) {
+                    seg = R[s]->pos - p;           // 'N' padding before the read (:506)
+                } else if (c[s].is < R[s]->len && c[s].k < R[s]->ncig) {
+                    if (c[s].op == 2) {
+                        kind[s] = 2;
+                        seg = c[s].rem;
+                    } else {
+                        kind[s] = 1;
+                        src[s] = c[s].is;
+                        const int64_t left = R[s]->len - c[s].is;
+                        seg = c[s].rem < left ? c[s].rem : left;
+                    }
+                }                                  // else 'N' padding after the read (:540)
+                n = seg < n ? seg : n;
+            }
+        }
+        if (t < col + n) {
+            for (int s = 0; s < 2; ++s)
+                if ((kind[s] & 1) && src[s] + (t - col) < R[s]->len) out[s] = src[s] + (t - col);
+            break;
+        }
+        for (int s = 0; s < 2; ++s)
+            if (kind[s]) {
+                c[s].rem -= n;
+                if (kind[s] != 2) c[s].is += n;
+                if (c[s].rem == 0) {
+                    ++c[s].k;
+                    bf_load(*R[s], c[s]);
+                }
+            }
+        col += n;
+        p += n;
+    }
+    ia = out[0];
+    ib = out[1];
+}
+
+__global__ __launch_bounds__(256) void k_base_filter(BaseFilterArgs A) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;
+    const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
+    const dcr_base_filter &T = A.flt;
+    const uint32_t skip = (uint32_t)(A.skip_below < 0 ? 0 : A.skip_below);
+    for (int64_t f = wave; f < A.n_fam; f += nw) {
+        if (A.fam_fail[f] != 0) {
+            if (lane_id() == 0) A.masked[f] = 0;
+            continue;
+        }
+        uint32_t masked = 0;
+        for (int j = 0; j < 2; ++j) {
+            const int64_t k = 2 * f + j, a = 4 * f + 2 * j;
+            BfRec S[2], R;
+            for (int s = 0; s < 2; ++s) {
+                bf_rec(A.ss, A.ss_col_off, a + s, A.ss_col, A.flag[a + s] != 0, S[s]);
+                if (!S[s].mapped) {                // min_pos of the strand's own layout: its reads' smallest start
+                    const int32_t r0 = A.sub_off[a + s], r1 = A.sub_off[a + s + 1];
+                    int32_t mp = 0x7fffffff;
+                    for (int32_t r = r0 + lane_id(); r < r1; r += kW) mp = A.read_pos[r] < mp ? A.read_pos[r] : mp;
+#pragma unroll
+                    for (int dd = 32; dd >= 1; dd >>= 1) {
+                        const int32_t o = __shfl_xor(mp, dd, kW);
+                        mp = o < mp ? o : mp;
+                    }
+                    S[s].t5 = r1 > r0 ? S[s].pos - (int64_t)mp : 0;
+                }
+            }
+            bf_rec(A.ds, A.ds_col_off, k, A.ds_col, A.flag[4 * (int64_t)A.n_fam + k] != 0, R);
+            const int64_t ro = A.ds_col_off[k];
+            const int64_t minpos = S[0].pos < S[1].pos ? S[0].pos : S[1].pos;
+            R.t5 = R.pos - minpos;
+            const uint32_t *aln = A.ds_aln + ro;
+            const bool lane_math = R.simple && S[0].simple && S[1].simple;
+            const int64_t L = R.len;
+            uint32_t *sq = reinterpret_cast<uint32_t *>(A.ds.seq + ro);
+            uint32_t *ql = reinterpret_cast<uint32_t *>(A.ds.qual + ro);
+            uint32_t n_m = 0;
+            for (int64_t w = lane_id(); 4 * w < L; w += kW) {
+                const uint32_t s0 = sq[w], q0 = ql[w];
+                const int nb = L - 4 * w < 4 ? (int)(L - 4 * w) : 4;
+                uint32_t s1 = s0, q1 = q0;
+                for (int i = 0; i < nb; ++i) {
+                    const uint32_t qb = (q0 >> (8 * i)) & 0xffu;
+                    if (qb < skip) continue;
+                    const int64_t bi = 4 * w + i;
+                    int64_t c, ca, cb;             // d-indices in r, a, b (-1: none)
+                    if (lane_math) {
+                        c = R.t5 + bi;
+                        const int64_t p = minpos + c;
+                        ca = bf_own_col(S[0], p - S[0].pos);
+                        cb = bf_own_col(S[1], p - S[1].pos);
+                    } else {
+                        int64_t t, ia, ib;
+                        if (R.mapped) {
+                            c = (int64_t)R.col[bi];
+                            t = (int64_t)aln[bi];
+                        } else {
+                            c = t = bf_own_col(R, bi);        // no '+' column: the d-index is the alignment column
+                        }
+                        bf_sources(S[0], S[1], minpos, t, ia, ib);
+                        ca = bf_own_col(S[0], ia);
+                        cb = bf_own_col(S[1], ib);
+                    }
+                    const bool va = ca >= 0 && ca < S[0].nde, vb = cb >= 0 && cb < S[1].nde;
+                    const int32_t aD = va ? S[0].d[ca] : 0, aE = va ? S[0].e[ca] : 0;
+                    const int32_t bD = vb ? S[1].d[cb] : 0, bE = vb ? S[1].e[cb] : 0;
+                    const int32_t cE = (c >= 0 && c < R.nde) ? R.e[c] : 0;
+                    bool m = false;
+                    if (T.active & DCR_BF_MIN_READS) {
+                        const int32_t hi = aD > bD ? aD : bD, lo = aD > bD ? bD : aD;
+                        m |= !(aD + bD >= T.min_reads[0] && hi >= T.min_reads[1] && lo >= T.min_reads[2]);
+                    }
+                    if (T.active & DCR_BF_ERROR_RATE) m |= (double)(aE + bE) > T.max_error_rate * (double)(aD + bD);
+                    if (T.active & DCR_BF_AGREEMENT) m |= cE > 0;
+                    if (m) {
+                        const uint32_t q2 = qb < 2 ? qb : 2;
+                        s1 = (s1 & ~(0xffu << (8 * i))) | ((uint32_t)'N' << (8 * i));
+                        q1 = (q1 & ~(0xffu << (8 * i))) | (q2 << (8 * i));
+                        // k_filter masks and counts whatever it then finds below its bound, this base
+                        // at its new quality included: count here only what it will not count again
+                        n_m += q2 >= skip ? 1u : 0u;
+                    }
+                }
+                if (s1 != s0) sq[w] = s1;
+                if (q1 != q0) ql[w] = q1;
+            }
+            masked += wave_sum(n_m);
+        }
+        if (lane_id() == 0) A.masked[f] = (int32_t)masked;
     }
 }
 

@@ -177,6 +177,15 @@ class DcrFilter(ctypes.Structure):
                 ("min_mean_base_quality", ctypes.c_double)]
 
 
+# ---- per-base consensus filters (include/dcr.h dcr_base_filter) ------------------
+BF_MIN_READS, BF_ERROR_RATE, BF_AGREEMENT = 1, 2, 4
+
+
+class DcrBaseFilter(ctypes.Structure):
+    """Mirror of ``dcr_base_filter`` (include/dcr.h)."""
+    _fields_ = [("active", ctypes.c_int32), ("min_reads", ctypes.c_int32 * 3), ("max_error_rate", ctypes.c_double)]
+
+
 # ---- consensus QC tables (include/dcr.h dcr_metrics; --metrics_output) ----------
 MET_READS_BINS, MET_DEPTH_BINS, MET_ERR_BINS, MET_QUAL_BINS, MET_COL_BINS = 256, 64, 1002, 256, 512
 
@@ -280,6 +289,18 @@ def filter_max_no_call_fraction(text):
     return _unit(text)
 
 
+def filter_min_base_reads(text):
+    """``T[,A[,B]]`` per base: parsed and checked as ``--filter_min_reads`` is."""
+    t, a, b = _numbers(text, int, 3, "--filter_min_base_reads")
+    if not (t >= a >= b):
+        raise ValueError("--filter_min_base_reads T,A,B needs T >= A >= B")
+    return (t, a, b)
+
+
+def filter_max_base_error_rate(text):
+    return _unit(text)
+
+
 def filter_min_mean_base_quality(text):
     v = float(text)
     if not 0.0 <= v < math.inf:
@@ -295,13 +316,38 @@ class ConsensusFilter:
     max_read_error_rate: object = None       # (C, S)
     max_no_call_fraction: object = None      # float
     min_mean_base_quality: object = None     # float
+    # the per-base rules (include/dcr.h dcr_base_filter; device writer only)
+    min_base_reads: object = None            # (T, A, B)
+    max_base_error_rate: object = None       # float
+    require_strand_agreement: bool = False
 
     @classmethod
     def from_args(cls, args):
         """The filter of a parsed command line, or None when no option is given."""
         f = cls(args.filter_min_base_quality, args.filter_min_reads, args.filter_max_read_error_rate,
-                args.filter_max_no_call_fraction, args.filter_min_mean_base_quality)
-        return f if f.active else None
+                args.filter_max_no_call_fraction, args.filter_min_mean_base_quality,
+                getattr(args, "filter_min_base_reads", None), getattr(args, "filter_max_base_error_rate", None),
+                bool(getattr(args, "filter_require_strand_agreement", False)))
+        return f if f.active or f.base_active else None
+
+    @property
+    def base_active(self) -> int:
+        """The DCR_BF_* bits of the per-base rules that are on."""
+        return ((BF_MIN_READS if self.min_base_reads is not None else 0)
+                | (BF_ERROR_RATE if self.max_base_error_rate is not None else 0)
+                | (BF_AGREEMENT if self.require_strand_agreement else 0))
+
+    def as_base_struct(self):
+        """``dcr_base_filter`` of the per-base rules, or None when none is on."""
+        if not self.base_active:
+            return None
+        s = DcrBaseFilter()
+        s.active = self.base_active
+        clamp = lambda v: max(-(1 << 31), min(v, (1 << 31) - 1))      # noqa: E731
+        for i, v in enumerate(self.min_base_reads or (0, 0, 0)):
+            s.min_reads[i] = clamp(v)
+        s.max_error_rate = self.max_base_error_rate or 0.0
+        return s
 
     @property
     def active(self) -> int:

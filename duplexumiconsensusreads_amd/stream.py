@@ -215,6 +215,8 @@ class DeviceStream:
     ``filter`` (set per run too): a params.ConsensusFilter or None.  The
     device writer applies it (dcr_set_filter) and ``result`` carries
     ``fam_filt``; on the host path the caller filters (native_io.apply_filter).
+    Its per-base rules (dcr_set_base_filter) exist on the device writer only:
+    the column of a base is known to the kernels alone.
 
     ``metrics`` (set per run too): the device writer counts the consensus QC
     tables (dcr_set_metrics) and ``result`` carries them as ``metrics``; on the

@@ -284,6 +284,66 @@ int dcr_set_filter(dcr_ctx *ctx, const dcr_filter *filter);
  * when dcr_wait_write[_ss] returns.  NULL removes it. */
 int dcr_slot_filter_out(dcr_ctx *ctx, int slot, int32_t *fam_filt);
 
+/* Per-base consensus filters (not a reference feature; the per-base rules of
+ * fgbio's FilterConsensusReads: --min-reads per base and
+ * --require-single-strand-agreement).  They mask single duplex bases by the
+ * raw-read support and the agreement at the alignment column the base came
+ * from.  oracle/dcr_oracle.py (consensus_core, reconstruct) is the
+ * executable form of the alignment; tests/base_filter_model.py restates the
+ * rules over it.
+ *
+ * Level 1, the column of a base.  For a consensus record (single-strand s or
+ * duplex r) let cons be the aligned consensus string (what consensus_core
+ * returns as cons: one char per alignment column, '+' where an insertion
+ * column was called absent, '-' for a deletion, lower case for a called
+ * insertion).  The d-index of a column counts the columns before it whose
+ * cons is not '+', so the d / e lists have one entry per d-index (n_de of
+ * them).  [t5, t3) is the window the 'N' trim leaves (:770-784; upper-case
+ * 'N' only).  Base i of seq is the i-th column inside the window whose cons
+ * is neither '+' nor '-'; col(i) is that column's d-index.
+ *
+ * Level 2, the source bases of a duplex column.  Duplex record r = 2f + j is
+ * called from the single-strand records a = 4f + 2j and b = a + 1, laid out
+ * as reconstruct([pos_a, pos_b], [cigar_a, cigar_b], [seq_a, seq_b], ..) lays
+ * them out (:430-547), quirks included: a column in which either strand's
+ * current CIGAR operation is I is an insertion column (the other strand gets
+ * '+') and still consumes one reference position, and the layout ends at
+ * max(pos + len(seq)).  Every duplex alignment column then holds, per
+ * strand, a base index ia / ib into that strand's seq, or nothing ('N'
+ * padding, '-', '+').
+ *
+ * For duplex base i at alignment column t with c = col_r(i):
+ *   aD = ss.d[a][col_a(ia)], aE = ss.e[a][col_a(ia)]  (0, 0 when strand a has
+ *   no base in column t); bD, bE likewise; cE = ds.e[r][c].
+ * Rules (each masks the base exactly as DCR_FILT_MASK_BASES does: 'N',
+ * quality min(q, 2), nothing else of the record touched, no re-trim):
+ *   DCR_BF_MIN_READS   keep iff aD + bD >= min_reads[0], max(aD, bD) >= [1],
+ *                      min(aD, bD) >= [2]
+ *   DCR_BF_ERROR_RATE  mask iff (double)(aE + bE) > max_error_rate *
+ *                      (double)(aD + bD)   (one double multiply, no fused
+ *                      contraction)
+ *   DCR_BF_AGREEMENT   mask iff cE > 0
+ * The bases masked are the union of these and of DCR_FILT_MASK_BASES; the
+ * masking comes before the record rules DCR_FILT_NO_CALL and
+ * DCR_FILT_MEAN_QUAL count 'N' and sum qualities, and fam_filt[f] >> 8 counts
+ * every masked base once.  Failing families are not touched.  With a base
+ * filter set, fam_filt is produced (dcr_slot_filter_out) as with a filter. */
+#define DCR_BF_MIN_READS 1
+#define DCR_BF_ERROR_RATE 2
+#define DCR_BF_AGREEMENT 4
+typedef struct dcr_base_filter {
+    int32_t active;               /* DCR_BF_* bits; 0: off                     */
+    int32_t min_reads[3];         /* total, larger strand, smaller strand      */
+    double max_error_rate;        /* in [0, 1]                                 */
+} dcr_base_filter;
+/* NULL or active == 0: off (the default; nothing is launched, copied, zeroed
+ * or allocated).  Holds for the batches submitted after the call.
+ * dcr_slot_fetch what 6 (a batch submitted with a base filter set): one byte
+ * per record, single-strand 4F then duplex 2F, 1 where the consensus kernels
+ * stored the record's column map (it has insertion columns), 0 where the map
+ * follows from pos and CIGAR (diagnostic; the tests read it). */
+int dcr_set_base_filter(dcr_ctx *ctx, const dcr_base_filter *filter);
+
 /* Consensus QC tables (not a reference feature; what fgbio's
  * CollectDuplexSeqMetrics / ErrorRateByReadPosition read off the written
  * file).  With metrics on, dcr_submit_write[_ss] counts, over the families f
