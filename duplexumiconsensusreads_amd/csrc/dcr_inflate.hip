@@ -145,8 +145,9 @@ __device__ __forceinline__ uint32_t dist_entry(uint32_t sym) {
 
 // Canonical decode tables from code lengths lens[0, n) (n <= 288), built by
 // the whole wave.  kind: 0 literal/length, 1 distance, 2 code-length code.
-// Returns false for an over-subscribed code.  Entries of codes longer than
-// TB bits are 0; an incomplete code leaves K_BAD entries.
+// Returns false for an over-subscribed code and for an incomplete one other
+// than the two zlib accepts (below).  Entries of codes longer than TB bits
+// are 0; the unused codes of an accepted incomplete code are K_BAD entries.
 template <int TB, int KIND>
 __device__ __noinline__ bool build_table(const uint8_t *lens, int n, uint32_t *tab, uint16_t *cnt_out, uint16_t *sym_out) {
     const int lane = lane_id();
@@ -166,7 +167,16 @@ __device__ __noinline__ bool build_table(const uint8_t *lens, int n, uint32_t *t
     // Kraft sum: sum cnt[L] 2^(15-L) <= 2^15
     uint32_t kr = lane >= 1 && lane <= 15 ? mycnt << (15 - lane) : 0;
     for (int d = 32; d >= 1; d >>= 1) kr += __shfl_xor(kr, d, kW);
-    if (uni(kr) > 32768u) return false;
+    kr = uni(kr);
+    if (kr > 32768u) return false;
+    // an incomplete code is rejected at the header, as zlib and libdeflate
+    // (the host pool) do: a code-length code has to be complete; a
+    // literal/length or distance code may also be a single 1-bit code, and a
+    // distance code may have no codes at all
+    if (kr != 32768u) {
+        const bool one_bit = kr == 16384u && lane_read(mycnt, 1) == 1;
+        if (KIND == 2 || !(one_bit || (KIND == 1 && kr == 0))) return false;
+    }
     // offsets (symbols of shorter codes) and canonical first codes
     uint32_t offs = 0, first = 0;
 #pragma unroll

@@ -7,17 +7,22 @@ import struct
 import zlib
 
 
-def bgzf_block(data: bytes, level=1) -> bytes:
-    c = zlib.compressobj(level, zlib.DEFLATED, -15)
-    cdata = c.compress(data) + c.flush()
+def bgzf_block(data: bytes, level=1, encode=None) -> bytes:
+    if encode is None:
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
+        cdata = c.compress(data) + c.flush()
+    else:
+        cdata = encode(data)
     bsize = 12 + 6 + len(cdata) + 8
+    assert bsize <= 65536
     head = b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize - 1)
     return head + cdata + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data))
 
 
-def reblock(src: str, dst: str, lo: int, hi: int, seed: int = 0, level: int = 1) -> int:
+def reblock(src: str, dst: str, lo: int, hi: int, seed: int = 0, level: int = 1, encode=None) -> int:
     """Rewrite a BGZF file with blocks of lo..hi uncompressed bytes (BGZF allows
-    any size up to 64 KiB); returns the block count."""
+    any size up to 64 KiB); returns the block count.  ``encode(data)`` returns
+    a block's raw DEFLATE bytes in place of zlib at ``level``."""
     raw = gzip.decompress(open(src, "rb").read())
     rng = random.Random(seed)
     n = 0
@@ -25,7 +30,7 @@ def reblock(src: str, dst: str, lo: int, hi: int, seed: int = 0, level: int = 1)
         p = 0
         while p < len(raw):
             k = rng.randint(lo, hi)
-            f.write(bgzf_block(raw[p:p + k], level))
+            f.write(bgzf_block(raw[p:p + k], level, encode))
             p += k
             n += 1
         f.write(bgzf_block(b""))

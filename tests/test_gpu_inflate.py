@@ -1,11 +1,15 @@
 """The device BGZF inflater (csrc/dcr_inflate.hip, include/dcr_inflate.h)
 against zlib on the same members: every block type (stored, fixed, dynamic),
 several blocks per member and sync-flush stored blocks between them,
-distances beyond the kernel's 8 KiB LDS history, periods below a wave,
+distances beyond the kernel's 4 KiB LDS history, periods below a wave,
 65,536-byte and empty members, output offsets that are not dword aligned, the
-native writer's BAMs at levels 1 and 6; and corrupted members reported by
-index without touching memory outside the batch (reference: the BAM read
-under ``samfile.fetch`` DuplexUMIConsensusReads.py:1476, :1519)."""
+native writer's BAMs at levels 1, 6, 9 and 12 (libdeflate's greedy, lazy and
+near-optimal parsers); corrupted members reported by index without touching
+memory outside the batch; and both inflate paths, the device stream and the
+host's libdeflate pool, on a BAM re-encoded by tests/deflate_builder.py into
+streams no compressor emits (reference: the BAM read under ``samfile.fetch``
+DuplexUMIConsensusReads.py:1476, :1519).  The hand-built members themselves
+are tests/test_gpu_inflate_streams.py."""
 import os
 import struct
 import zlib
@@ -67,7 +71,7 @@ def test_inflate_block_types_and_edges(inf):
     cases = [
         text[:60_000], rnd[:20_000],                                     # dynamic / stored (incompressible)
         member_data := text[:40_000],
-        rnd[:9_000] * 4,                                                 # distances > 8 KiB
+        rnd[:9_000] * 4,                                                 # distances beyond the 4 KiB ring
         b"ab" * 20_000, b"xyz0123456789" * 3000,                        # periods below 64, length-258 runs
         bytes(65536),                                                    # a full 64 KiB member
         b"", b"A", b"ACGT" * 3 + b"N",
@@ -100,7 +104,7 @@ def test_inflate_block_types_and_edges(inf):
     assert member_data in want
 
 
-@pytest.mark.parametrize("level", [1, 6])
+@pytest.mark.parametrize("level", [1, 6, 9, 12])
 def test_inflate_native_writer_bam(inf, tmp_path, level):
     path = str(tmp_path / "c2.bam")
     synth.write_packed_bam(path, synth.packed_fixed_size(20_000, seed=3), seed=3, level=level)
@@ -266,3 +270,127 @@ def test_stream_ranged_ingest_same_batches_as_host_inflate(tmp_path):
         h = _with_gpu_inflate("0", lambda: ingest_digest(inp, lo, hi))
         assert g[3] and not h[3]
         assert g[:3] == h[:3], (lo, hi)
+
+
+def builder_encode(seed, incomplete=False):
+    """An ``encode`` for bgzf_util.reblock: the greedy tokenizer at maximum
+    distance 32,768 (the farthest of equally long candidates), a block switch
+    every few hundred tokens, blocks cycling through dynamic with stretched
+    code lengths (15-bit codes), fixed, stored and empty stored.
+    ``incomplete``: one dynamic block whose literal/length code has a code
+    lengthened by a bit, so that the code is incomplete; its unused code
+    never occurs."""
+    import random
+
+    from . import deflate_builder as db
+    rng = random.Random(seed)
+    state = {"k": 0}
+
+    def encode(data):
+        toks = db.tokenize(data, 32768, far=True)
+        s, p, done = db.Stream(), 0, bytearray()
+        if incomplete:
+            fl, fd = db.token_freqs(toks)
+            ll = db.huffman_lengths(fl)
+            ll[max(range(286), key=lambda i: (ll[i] < 15, ll[i]))] += 1
+            assert db.kraft(ll) < 32768
+            s.dynamic(toks, ll, db.huffman_lengths(fd) if any(fd) else [0], final=True)
+            return s.getvalue()
+        while True:
+            n = rng.randint(200, 600)
+            part, p = toks[p:p + n], p + n
+            final = p >= len(toks)
+            kind = state["k"] % 4
+            state["k"] += 1
+            if kind == 0:
+                fl, fd = db.token_freqs(part)
+                s.dynamic(part, db.stretched_lengths(fl), db.stretched_lengths(fd) if any(fd) else [0], final=final)
+            elif kind == 1:
+                s.fixed(part, final=final)
+            elif kind == 2:
+                s.stored(db.replay(part, bytes(done)), final=final)
+            else:
+                s.stored(b"")
+                s.fixed(part, final=final)
+            done += db.replay(part, bytes(done))
+            if final:
+                return s.getvalue()
+    return encode
+
+
+@pytest.fixture(scope="module")
+def reencoded_bam(tmp_path_factory):
+    """About 1,000 reads, re-encoded into members of 0.5-60 KiB by the builder."""
+    from .bgzf_util import reblock
+    d = tmp_path_factory.mktemp("reenc")
+    src, dst = str(d / "src.bam"), str(d / "reenc.bam")
+    synth.write_packed_bam(src, synth.packed_fixed_size(32, seed=21), seed=21, level=6)
+    n = reblock(src, dst, 512, 60 * 1024, seed=7, encode=builder_encode(7))
+    assert n >= 8
+    from duplexumiconsensusreads_amd import bam
+    assert bam.bgzf_stream(dst) == bam.bgzf_stream(src)             # zlib reads the same bytes
+    return src, dst, n
+
+
+def test_reencoded_bam_same_records_on_both_inflate_paths(tmp_path, reencoded_bam):
+    """Streams no compressor emits (15-bit codes, far matches, block kinds
+    switching every few hundred tokens) through the streaming entry
+    (``dcr_inflate_stream_*``) and through the host's libdeflate pool: the
+    same batches, and the CLI's three outputs and stdout equal."""
+    from duplexumiconsensusreads_amd import bam
+    from .bgzf_util import ingest_digest
+    src, inp, _ = reencoded_bam
+    g = _with_gpu_inflate("1", lambda: ingest_digest(inp))
+    h = _with_gpu_inflate("0", lambda: ingest_digest(inp))
+    assert g[3] and not h[3]
+    assert g[:3] == h[:3]
+    assert g[:3] == _with_gpu_inflate("0", lambda: ingest_digest(src))[:3]
+    so_gpu = _cli(inp, str(tmp_path / "g.bam"), "1")
+    so_host = _cli(inp, str(tmp_path / "h.bam"), "0")
+    assert so_gpu == so_host
+    for suf in (".bam", "_filteredreads.bam", "_filteredfamilies.bam"):
+        assert bam.bgzf_stream(str(tmp_path / ("g" + suf))) == bam.bgzf_stream(str(tmp_path / ("h" + suf)))
+
+
+def _ingest_all(path):
+    from duplexumiconsensusreads_amd import native_io
+    ing = native_io.Ingest(path)
+    gpu = ing.gpu_inflate
+    hb = native_io.HostBatch(reads=1 << 20)
+    try:
+        while True:
+            ing.next(hb)
+            if hb.end_kind != native_io.END_FULL:
+                if hb.end_kind == native_io.END_ERROR:
+                    raise RuntimeError(hb.error()[1])
+                return gpu
+    finally:
+        ing.close()
+
+
+@pytest.mark.parametrize("gpu_inflate", ["1", "0"])
+def test_ingest_stops_on_incomplete_code_on_both_inflate_paths(tmp_path, reencoded_bam, gpu_inflate):
+    """One member in the middle of the file has an incomplete literal/length
+    code whose unused code never occurs: zlib and libdeflate reject the block
+    at its header, and so does the device inflater; the ingest stops with an
+    error on either path."""
+    import gzip
+
+    from duplexumiconsensusreads_amd import _lib
+    from .bgzf_util import bgzf_block
+    _, good, _ = reencoded_bam
+    blob = open(good, "rb").read()
+    m, _ = _lib.bgzf_members(blob)
+    x = m[len(m) // 2]
+    lo = int(x["in_off"]) - 18
+    hi = int(x["in_off"]) + int(x["in_len"]) + 8
+    data = gzip.decompress(blob[lo:hi])
+    assert len(data) == int(x["isize"]) > 0
+    bad_member = bgzf_block(data, encode=builder_encode(0, incomplete=True))
+    with pytest.raises(zlib.error, match="invalid literal/lengths set"):
+        zlib.decompress(bad_member[18:-8], -15)
+    inp = str(tmp_path / "incomplete.bam")
+    open(inp, "wb").write(blob[:lo] + bad_member + blob[hi:])
+    assert _with_gpu_inflate(gpu_inflate, lambda: _ingest_all(good)) == (gpu_inflate == "1")
+    with pytest.raises(Exception, match="failed to inflate"):
+        _with_gpu_inflate(gpu_inflate, lambda: _ingest_all(inp))
