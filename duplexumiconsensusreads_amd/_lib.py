@@ -49,6 +49,7 @@ EXPORTS = {
     "dcr_set_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "dcr_slot_filter_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "dcr_set_base_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "dcr_set_base_tags": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "dcr_set_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "dcr_slot_metrics_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     # include/dcr_inflate.h: BGZF inflate on the device
@@ -127,6 +128,7 @@ class Context:
         self.want_info = want_info
         self.filter = None
         self.metrics = False
+        self.base_tags = False
         if want_info:
             _check(lib.dcr_set_options(self._ctx, 1))
 
@@ -165,6 +167,14 @@ class Context:
             return
         _check(load().dcr_set_metrics(self._ctx, 1 if on else 0))
         self.metrics = bool(on)
+
+    def set_base_tags(self, on):
+        """The device writer writes the per-base tags (include/dcr.h
+        dcr_set_base_tags) for the batches it takes from now on, or not."""
+        if bool(on) == self.base_tags:
+            return
+        _check(load().dcr_set_base_tags(self._ctx, 1 if on else 0))
+        self.base_tags = bool(on)
 
     @property
     def stream(self):

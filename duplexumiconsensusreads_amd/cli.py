@@ -32,6 +32,13 @@ tables (include/dcr.h ``dcr_metrics``): family sizes, strand depths, error
 rates, base qualities and errors by read position of the consensus as called,
 before any filter; counted on the device beside the writer.  Off by default.
 
+``--per_base_tags`` (not a reference flag) writes the depth, error and strand
+tags ``ad bd cd ae be ce ac bc aq bq`` (and ``sd se`` of the single-strand
+reads) with one value per base of ``SEQ``, as ``B:s`` arrays and strings of the
+read's length, instead of the reference's lists per alignment column
+(include/dcr.h ``dcr_set_base_tags``; device writer only).  Off by default;
+without it no output byte changes.
+
 Batches are pipelined: a thread ingests batch k+1 while the device runs batch
 k and the main thread writes batch k-1.
 
@@ -129,6 +136,10 @@ def parse_args(argv):
     ap.add_argument("--metrics_output", required=False, default=None, type=str, metavar="FILE.json",
                     help="count family sizes, strand depths, error rates, qualities and errors by read position "
                          "of the consensus reads as called (before any --filter_*) into FILE.json")
+    # not a reference flag: the per-column tags per base of SEQ (include/dcr.h dcr_set_base_tags)
+    ap.add_argument("--per_base_tags", action="store_true",
+                    help="write ad bd cd ae be ce as B:s arrays and ac bc aq bq as strings with one value per base "
+                         "of SEQ (sd se of --single_strand_output likewise) instead of lists per alignment column")
     return ap.parse_args(argv)
 
 
@@ -271,11 +282,12 @@ def gpu_inflate(device: int = 0):
     return got[0]
 
 
-def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=False):
+def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=False, base_tags=False):
     """``ss_output``: this run also writes the single-strand records (a
     property of the run, set on the backend each time: the default backend
     is kept across runs).  ``flt``: this run's ConsensusFilter or None,
-    set each time in the same way; so is ``metrics`` (--metrics_output)."""
+    set each time in the same way; so are ``metrics`` (--metrics_output) and
+    ``base_tags`` (--per_base_tags)."""
     if backend is None:
         be = default_backend(params, device)
     elif hasattr(backend, "submit"):
@@ -298,6 +310,11 @@ def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=Fa
         be.metrics = metrics
     elif metrics:
         raise ValueError("this backend cannot count the consensus metrics")
+    if base_tags and not getattr(be, "device_writer", False):
+        # no host formatter for them: the column of a base is only known on the device
+        raise ValueError("this backend cannot write the per-base tags")
+    if hasattr(be, "base_tags"):
+        be.base_tags = base_tags
     return be
 
 
@@ -706,7 +723,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
     met_path, met_total, done = args.metrics_output, None, False
     try:
         be = _as_backend(backend, params, args.device, ss_path is not None, ConsensusFilter.from_args(args),
-                         met_path is not None)
+                         met_path is not None, args.per_base_tags)
         cons, excl, unproc, *rest = _open_writers(
             [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
              "%s_filteredfamilies.bam" % consensus_filename[:-4]] + ([ss_path] if ss_path else []), ing.header, args,
@@ -906,7 +923,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
                            params.min_base_quality, args.threads, rng_range[0], rng_range[1],
                            ss_meta=len(parts) > 3)
     be = _as_backend(backend, params, device, len(parts) > 3, ConsensusFilter.from_args(args),
-                     args.metrics_output is not None)
+                     args.metrics_output is not None, args.per_base_tags)
     cons, excl, unproc, *rest = _open_writers(parts, header, args, ing)
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng_state)

@@ -219,9 +219,10 @@ struct WriterBufs {
     uint32_t *tok;
     int32_t *fam_filt;      // k_filter's outcomes; null unless a filter is set (dcr_set_filter)
     dcr_metrics *metrics;   // k_metrics' accumulator; null unless metrics are on (dcr_set_metrics)
-    // null unless a base filter is set (dcr_set_base_filter): k_base_filter's count per family and
-    // the column maps k_consensus_general stores for it
+    // null unless a base filter is set (dcr_set_base_filter): k_base_filter's count per family
     int32_t *base_masked;
+    // null unless a base filter or the per-base tags (dcr_set_base_tags) are on: the column maps
+    // k_consensus_general_map stores for them
     dcr::BaseMap bmap;
 };
 
@@ -263,11 +264,13 @@ void plan_writer_ss(int64_t F, Plan &p, WriterSsBufs &ws) {
 // at most nbm blocks, gd k_deflate workgroups; with ws, the single-strand
 // stream's regions after them (the first stream's layout does not change)
 // and with filt, k_filter's outcomes (no region without it); with met,
-// k_metrics' accumulator (none without it); with bf (the batch, when a base
-// filter is set), k_base_filter's counts and the column maps, after every
-// other region (none without it)
+// k_metrics' accumulator (none without it); with bfilt (a base filter is set)
+// k_base_filter's counts and with maps (the batch, when a base filter or the
+// per-base tags are on) the column maps, after every other region (none
+// without them)
 void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w,
-                 WriterSsBufs *ws = nullptr, bool filt = false, bool met = false, const dcr_batch *bf = nullptr) {
+                 WriterSsBufs *ws = nullptr, bool filt = false, bool met = false, const dcr_batch *maps = nullptr,
+                 bool bfilt = false) {
     w.names = p.take<char>((size_t)n_names + 1);
     w.fam_code = p.take<int64_t>((size_t)F);
     w.fam_rx = p.take<int64_t>(2 * (size_t)F);
@@ -289,12 +292,12 @@ void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd
     if (ws) plan_writer_ss(F, p, *ws);
     w.base_masked = nullptr;
     w.bmap = dcr::BaseMap{};
-    if (bf) {
-        w.base_masked = p.take<int32_t>((size_t)F);
+    if (bfilt) w.base_masked = p.take<int32_t>((size_t)F);
+    if (maps) {
         w.bmap.flag = p.take<uint8_t>(6 * (size_t)F);
-        w.bmap.ss_col = p.take<uint32_t>((size_t)bf->ss_cols);
-        w.bmap.ds_col = p.take<uint32_t>((size_t)bf->ds_cols);
-        w.bmap.ds_aln = p.take<uint32_t>((size_t)bf->ds_cols);
+        w.bmap.ss_col = p.take<uint32_t>((size_t)maps->ss_cols);
+        w.bmap.ds_col = p.take<uint32_t>((size_t)maps->ds_cols);
+        w.bmap.ds_aln = p.take<uint32_t>((size_t)maps->ds_cols);
     }
 }
 }  // namespace
@@ -334,7 +337,7 @@ struct dcr_ctx {
         // the single-strand stream of dcr_submit_write_ss (writer_ss)
         int64_t *d_ss_rec_off = nullptr;
         uint8_t *d_ss_stream = nullptr, *d_ss_comp = nullptr;
-        uint8_t *d_map_flag = nullptr;   // the batch's BaseMap::flag when a base filter was set, else null
+        uint8_t *d_map_flag = nullptr;   // the batch's BaseMap::flag when a base filter or base tags were on, else null
         int64_t n_fam = 0;
         bool writer = false, writer_ss = false;
         hipEvent_t ev_h2d = nullptr, ev_comp = nullptr, ev_d2h = nullptr;
@@ -353,8 +356,9 @@ struct dcr_ctx {
     dcr_filter filter{};    // dcr_set_filter; active == 0: off
     bool metrics = false;   // dcr_set_metrics
     dcr_base_filter base_filter{};   // dcr_set_base_filter; active == 0: off
+    bool base_tags = false;          // dcr_set_base_tags
     // the column maps of the batch being submitted (submit_write sets them around its
-    // dcr_run_batch when a base filter is set); all null otherwise
+    // dcr_run_batch when a base filter or the per-base tags are on); all null otherwise
     dcr::BaseMap bmap{};
     // fast-kernel constants (fast_constants)
     uint32_t fast_kq = 0, fast_kqlo = 0;
@@ -608,7 +612,7 @@ static int launch_strand(dcr_ctx *c, dcr::Args &a, const dcr_batch *in, const dc
     // after k_decide_deep: it reads the general list's entries, which
     // k_ins_layout marks decided (bit 31) for the records it decides
     hipLaunchKernelGGL(dcr::k_ins_layout<DUPLEX>, dim3(grid_for(2048)), dim3(256), 0, c->stream, a);
-    // with a base filter set, the instantiation that also stores the base maps
+    // with a base filter or the per-base tags on, the instantiation that also stores the base maps
     if (c->bmap.flag)
         hipLaunchKernelGGL(dcr::k_consensus_general_map<DUPLEX>, dim3(grid_for(1024)), dim3(256), 0, c->stream, a, c->bmap);
     else
@@ -976,8 +980,24 @@ int dcr_wait(dcr_ctx *c, int slot) {
 // ---- device record writer ----------------------------------------------------
 
 // Upper bound of the formatted duplex records of a batch (dcr_writer.hip
-// rec_size): regions bound lengths, CIGARs and depth lists.
-static int64_t stream_bound(const dcr_batch *h, const dcr_wmeta *m) {
+// rec_size): regions bound lengths, CIGARs and depth lists.  Per record, with
+// Td / Ta / Tb the columns of its own and its two strands' regions:
+//   fixed parts  36 core + 29 + lc name + (4 + lc) MI + (4 + lr) RX + 26 + reads
+//                aQ bQ cQ + at most 42 aD..cM + 21 aE..cE + the heads of the ten
+//                per-column tags (at most 6 * 8 + 4 * 4 = 64): under 400 + 2 lc +
+//                lr + reads
+//   default      per column of Td 4 CIGAR + 1.5 SEQ / QUAL + 2 * 7 of the cd /
+//                ce list entries ("65535, "): 19.5 <= 20; per column of Ta / Tb
+//                2 * 7 of ad / ae + 2 of ac / aq: 16
+//   tags         (rec_size_tags) len <= Td bases and n_cig <= Td: 4 CIGAR + 0.5 +
+//                1 SEQ / QUAL (+ 0.5 for an odd len) + 6 * 2 of the B:s arrays + 4
+//                of the strings = 21.5 Td + 0.5 <= 22 Td; nothing per strand column
+// Neither bound can be exceeded by a batch whose records stay inside their
+// regions (the kernels raise DCR_ECAPACITY otherwise).  The compressed blocks
+// are another matter: the caller's cap_bgzf is checked against totals[0] in
+// fetch_blocks, and a slot whose blocks do not fit is fetched again
+// (dcr_slot_fetch what 2 / 5); tagged records take that path like any other.
+static int64_t stream_bound(const dcr_batch *h, const dcr_wmeta *m, bool tags) {
     int64_t B = 0;
     for (int32_t f = 0; f < h->n_fam; ++f) {
         const int64_t lc = (int64_t)std::strlen(m->names + m->fam_code[f]);
@@ -987,7 +1007,7 @@ static int64_t stream_bound(const dcr_batch *h, const dcr_wmeta *m) {
             const int64_t Ta = h->ss_col_off[a + 1] - h->ss_col_off[a];
             const int64_t Tb = h->ss_col_off[b + 1] - h->ss_col_off[b];
             const int64_t lr = (int64_t)std::strlen(m->names + m->fam_rx[2 * f + j]);
-            B += 400 + 2 * lc + lr + 20 * Td + 16 * (Ta + Tb) + (h->sub_off[a + 1] - h->sub_off[a]) +
+            B += 400 + 2 * lc + lr + (tags ? 22 * Td : 20 * Td + 16 * (Ta + Tb)) + (h->sub_off[a + 1] - h->sub_off[a]) +
                  (h->sub_off[b + 1] - h->sub_off[b]);
         }
     }
@@ -996,14 +1016,18 @@ static int64_t stream_bound(const dcr_batch *h, const dcr_wmeta *m) {
 
 // Upper bound of the formatted single-strand records of a batch
 // (dcr_writer.hip rec_size_ss): per column of the region at most 4 bytes of
-// CIGAR, 1.5 of sequence and quality and 7 + 7 of the two depth lists.
-static int64_t stream_bound_ss(const dcr_batch *h, const dcr_wmeta *m, const dcr_wmeta_ss *ms) {
+// CIGAR, 1.5 of sequence and quality and 7 + 7 of the two depth lists: 19.5 <=
+// 20.  With the per-base tags (rec_size_ss_tags) the lists are two B:s arrays
+// of len <= T entries: 4 + 1.5 + 2 * 2 = 9.5 T + 0.5 <= 10 T; the fixed parts
+// (36 + 20 + lc + 8 + lmi + lrx + 8 + reads + 14 sD sM + 7 sE + 16 array
+// heads = 109 + ...) stay under 160 either way.
+static int64_t stream_bound_ss(const dcr_batch *h, const dcr_wmeta *m, const dcr_wmeta_ss *ms, bool tags) {
     int64_t B = 0;
     for (int32_t f = 0; f < h->n_fam; ++f) {
         const int64_t lc = (int64_t)std::strlen(m->names + m->fam_code[f]);
         for (int s = 4 * f; s < 4 * f + 4; ++s)
             B += 160 + lc + (int64_t)std::strlen(m->names + ms->sub_mi[s]) + (int64_t)std::strlen(m->names + ms->sub_rx[s]) +
-                 20 * (h->ss_col_off[s + 1] - h->ss_col_off[s]) + (h->sub_off[s + 1] - h->sub_off[s]);
+                 (tags ? 10 : 20) * (h->ss_col_off[s + 1] - h->ss_col_off[s]) + (h->sub_off[s + 1] - h->sub_off[s]);
     }
     return B;
 }
@@ -1025,29 +1049,31 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     Plan p{(char *)S.buf.p};
     plan_io(h, p, &db, dout);
     // writer buffers
-    const int64_t B = stream_bound(h, m);
+    const bool btags = c->base_tags;
+    const int64_t B = stream_bound(h, m, btags);
     const int64_t nbm = B / (int64_t)dfl::kMaxIn + 2;
     const unsigned gd = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nbm, (int64_t)c->n_cu * c->dfl_blocks));
     WriterBufs wb;
     WriterSsBufs wsb{};
     if (ms) {
-        wsb.B = stream_bound_ss(h, m, ms);
+        wsb.B = stream_bound_ss(h, m, ms, btags);
         wsb.nbm = wsb.B / (int64_t)dfl::kMaxIn + 2;
         wsb.gd = (unsigned)std::max<int64_t>(1, std::min<int64_t>(wsb.nbm, (int64_t)c->n_cu * c->dfl_blocks));
     }
     // a base filter alone still gives fam_filt: k_filter runs to add the masked counts into it
     const bool bfilt = c->base_filter.active != 0;
     const bool filt = c->filter.active != 0 || bfilt;
+    const bool maps = bfilt || btags;       // the column maps: planned, zeroed and filled for either
     if (filt && F && !S.h_fam_filt)
         return fail(DCR_EARG, "a filter is set but the slot has no fam_filt destination (dcr_slot_filter_out)");
     const bool met = c->metrics;
     if (met && !S.h_metrics)
         return fail(DCR_EARG, "metrics are on but the slot has no destination (dcr_slot_metrics_out)");
     Plan wsz;
-    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met, bfilt ? h : nullptr);
+    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt);
     if (wsz.off > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wsz.off + wsz.off / 8));
     Plan wp{(char *)S.wbuf.p};
-    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met, bfilt ? h : nullptr);
+    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt);
     // H2D: inputs and writer metadata on the copy stream
     HIP_TRY(upload_inputs(h, db, c->s_h2d));
     if (m->n_names) HIP_TRY(hipMemcpyAsync(wb.names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
@@ -1061,9 +1087,9 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         HIP_TRY(hipMemcpyAsync(wsb.sub_mi, ms->sub_mi, 32 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
         HIP_TRY(hipMemcpyAsync(wsb.sub_rx, ms->sub_rx, 32 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
     }
-    // with a base filter the general kernels store the column maps of the records with
-    // insertion columns and flag them; the flags start from zero for every batch
-    if (bfilt && F) HIP_TRY(hipMemsetAsync(wb.bmap.flag, 0, 6 * (size_t)F, c->stream));
+    // with a base filter or the per-base tags the general kernels store the column maps of the
+    // records with insertion columns and flag them; the flags start from zero for every batch
+    if (maps && F) HIP_TRY(hipMemsetAsync(wb.bmap.flag, 0, 6 * (size_t)F, c->stream));
     c->bmap = wb.bmap;
     rc = slot_run(c, S, h, &db, dout);
     c->bmap = dcr::BaseMap{};
@@ -1122,10 +1148,19 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
             hipLaunchKernelGGL(dcrw::k_filter, dim3(gf), dim3(256), 0, c->stream, Fa);
         }
         const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((2 * F + 3) / 4, (int64_t)c->n_cu * 8));
-        hipLaunchKernelGGL(dcrw::k_fmt_size, dim3(g), dim3(256), 0, c->stream, A);
+        if (btags)
+            hipLaunchKernelGGL(dcrw::k_fmt_size_tags, dim3(g), dim3(256), 0, c->stream, A);
+        else
+            hipLaunchKernelGGL(dcrw::k_fmt_size, dim3(g), dim3(256), 0, c->stream, A);
         HIP_TRY(hipGetLastError());
         HIP_TRY(dcrw::scan_excl_i64(wb.rec_size, wb.rec_off, (int)(2 * F + 1), wb.scan, c->stream));
-        hipLaunchKernelGGL(dcrw::k_fmt_write, dim3(g), dim3(256), 0, c->stream, A);
+        if (btags) {
+            // after the filters like k_fmt_write: it copies the masked seq / qual, and reads nothing else they write
+            dcrw::FmtTagArgs At{A, db.read_pos, wb.bmap.ss_col, wb.bmap.ds_col, wb.bmap.ds_aln, wb.bmap.flag};
+            hipLaunchKernelGGL(dcrw::k_fmt_write_tags, dim3(g), dim3(256), 0, c->stream, At);
+        } else {
+            hipLaunchKernelGGL(dcrw::k_fmt_write, dim3(g), dim3(256), 0, c->stream, A);
+        }
         HIP_TRY(hipGetLastError());
     } else {
         HIP_TRY(hipMemsetAsync(wb.rec_off, 0, 8, c->stream));
@@ -1162,10 +1197,18 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         HIP_TRY(hipMemsetAsync(wsb.bsz, 0, 8 * (size_t)(wsb.nbm + 2), c->stream));
         if (F) {
             const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)c->n_cu * 8));
-            hipLaunchKernelGGL(dcrw::k_fmt_size_ss, dim3(g), dim3(256), 0, c->stream, As);
+            if (btags)
+                hipLaunchKernelGGL(dcrw::k_fmt_size_ss_tags, dim3(g), dim3(256), 0, c->stream, As);
+            else
+                hipLaunchKernelGGL(dcrw::k_fmt_size_ss, dim3(g), dim3(256), 0, c->stream, As);
             HIP_TRY(hipGetLastError());
             HIP_TRY(dcrw::scan_excl_i64(wsb.rec_size, wsb.rec_off, (int)(4 * F + 1), wsb.scan, c->stream));
-            hipLaunchKernelGGL(dcrw::k_fmt_write_ss, dim3(g), dim3(256), 0, c->stream, As);
+            if (btags) {
+                dcrw::FmtSsTagArgs Ast{As, db.read_pos, wb.bmap.ss_col, wb.bmap.flag};
+                hipLaunchKernelGGL(dcrw::k_fmt_write_ss_tags, dim3(g), dim3(256), 0, c->stream, Ast);
+            } else {
+                hipLaunchKernelGGL(dcrw::k_fmt_write_ss, dim3(g), dim3(256), 0, c->stream, As);
+            }
             HIP_TRY(hipGetLastError());
         } else {
             HIP_TRY(hipMemsetAsync(wsb.rec_off, 0, 8, c->stream));
@@ -1256,6 +1299,12 @@ int dcr_set_metrics(dcr_ctx *c, int on) {
     return DCR_OK;
 }
 
+int dcr_set_base_tags(dcr_ctx *c, int on) {
+    if (!c) return fail(DCR_EARG, "NULL context");
+    c->base_tags = on != 0;
+    return DCR_OK;
+}
+
 int dcr_slot_metrics_out(dcr_ctx *c, int slot, dcr_metrics *pinned_dst) {
     if (!c || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
     if (c->slots[slot].busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
@@ -1340,7 +1389,7 @@ int dcr_slot_fetch(dcr_ctx *c, int slot, int what, int64_t off, int64_t n, void 
             if (n) HIP_TRY(hipMemcpy(dst, S.d_ss_comp + off, (size_t)n, hipMemcpyDeviceToHost));
         }
     } else if (what == 6) {
-        if (!S.d_map_flag) return fail(DCR_EARG, "slot's batch ran without a base filter");
+        if (!S.d_map_flag) return fail(DCR_EARG, "slot's batch ran without a base filter or the per-base tags");
         if (off + n > 6 * S.n_fam) return fail(DCR_EARG, "map flags out of range");
         if (n) HIP_TRY(hipMemcpy(dst, S.d_map_flag + off, (size_t)n, hipMemcpyDeviceToHost));
     } else {

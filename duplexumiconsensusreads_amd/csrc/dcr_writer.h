@@ -84,6 +84,21 @@ struct FmtSsArgs {
     uint8_t *stream;                // formatted records
 };
 
+// the per-base tags' writers (k_fmt_write_tags / k_fmt_write_ss_tags, dcr_set_base_tags): the
+// default writer's arguments and what the column of a base needs (as BaseFilterArgs)
+struct FmtTagArgs {
+    FmtArgs f;
+    const int32_t *read_pos;        // [n_reads]
+    const uint32_t *ss_col, *ds_col, *ds_aln;   // the stored maps (dcr::BaseMap)
+    const uint8_t *flag;            // [6F]
+};
+struct FmtSsTagArgs {
+    FmtSsArgs f;
+    const int32_t *read_pos;        // [n_reads]
+    const uint32_t *ss_col;
+    const uint8_t *flag;            // [6F]: the single-strand records' are the first 4F
+};
+
 struct DflArgs {
     const uint8_t *stream;
     const int64_t *stream_bytes;    // device scalar (rec_off[2F])
@@ -111,6 +126,10 @@ __global__ void k_fmt_size(FmtArgs A);
 __global__ void k_fmt_write(FmtArgs A);
 __global__ void k_fmt_size_ss(FmtSsArgs A);
 __global__ void k_fmt_write_ss(FmtSsArgs A);
+__global__ void k_fmt_size_tags(FmtArgs A);
+__global__ void k_fmt_write_tags(FmtTagArgs T);
+__global__ void k_fmt_size_ss_tags(FmtSsArgs A);
+__global__ void k_fmt_write_ss_tags(FmtSsTagArgs T);
 __global__ void k_deflate(DflArgs D);
 __global__ void k_compact(CompactArgs C);
 

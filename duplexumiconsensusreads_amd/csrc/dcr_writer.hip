@@ -5,7 +5,9 @@
 // (dcr_submit_write_ss) also the four single-strand records of every family,
 // as a second record stream compressed by the same kernels; and with a filter
 // set (dcr_set_filter) k_filter first, which masks weak duplex bases and marks
-// the families neither stream writes.
+// the families neither stream writes.  With the per-base tags on
+// (dcr_set_base_tags) kernels of their own format both streams, the default
+// ones staying as they are.
 //
 // Reference (/root/reference/DuplexUMIConsensusReads.py): record fields
 // make_consensus_read :1352-1384, names / flags :892-968, duplex tags
@@ -977,6 +979,322 @@ __global__ __launch_bounds__(256) void k_fmt_write_ss(FmtSsArgs A) {
         RecSs r;
         rec_setup_ss(A, (int32_t)s, r);
         rec_write_ss(A, r, A.stream + o, (uint32_t)n);
+    }
+}
+
+// ---- the per-base tags (dcr_set_base_tags; include/dcr.h states them).  The
+// six depth / error tags become B:s arrays and the four strand strings Z
+// strings of the record's own length, one value per base of SEQ, so the sizes
+// follow from len alone and the size kernels read no map.  The write kernels
+// are one wave per record like k_fmt_write[_ss]: the head through cQ / sQ is
+// rec_head[_ss]; then every lane finds the columns and source bases of its own
+// base once, as k_base_filter does (bf_rec, bf_own_col, bf_sources, the single
+// M run shortcut, the stored maps of the records that have them), and stores
+// its element of every tag, whose offsets inside the record are known up
+// front.  Records start at any byte offset: the 16-bit elements go out as two
+// byte stores.  No LDS.  Every index is clamped to its region (bf_rec), and a
+// base at or past the clamped length gets the absent-strand values.
+constexpr uint32_t kTagArr = 8;     // tag, 'B', 's', count
+constexpr uint32_t kTagStr = 4;     // tag, 'Z', NUL
+
+__device__ __forceinline__ uint32_t tags_size(int32_t L) {
+    return 6 * (kTagArr + 2u * (uint32_t)L) + 4 * (kTagStr + (uint32_t)L);
+}
+
+__device__ uint32_t rec_size_tags(const FmtArgs &A, const Rec &r) {
+    const dcr_out &ss = A.ss, &ds = A.ds;
+    uint32_t n = 36 + 16 + r.lc + 12 + 1 + 4u * (uint32_t)r.nc + (uint32_t)((r.L + 1) >> 1) + (uint32_t)r.L;
+    n += 3 + r.lc + 1 + 3 + r.lr + 1;                                  // MI, RX
+    n += 8 + (uint32_t)(r.a1 - r.a0) + 8 + (uint32_t)(r.b1 - r.b0) + 8 + 2;   // aQ bQ cQ
+    n += int_tag_bytes(ss.D[r.a]) + int_tag_bytes(ss.D[r.b]) + int_tag_bytes(ds.D[r.k]);
+    n += int_tag_bytes(ss.M[r.a]) + int_tag_bytes(ss.M[r.b]) + int_tag_bytes(ds.M[r.k]);
+    n += 3 * 7;
+    return n + tags_size(r.L);
+}
+
+// t5 of a record without a stored map: pos - the smallest start of its reads (k_base_filter's wave minimum)
+__device__ int64_t tag_t5(const int32_t *sub_off, const int32_t *read_pos, int64_t s, int64_t pos) {
+    const int32_t r0 = sub_off[s], r1 = sub_off[s + 1];
+    int32_t mp = 0x7fffffff;
+    for (int32_t r = r0 + lane_id(); r < r1; r += kW) mp = read_pos[r] < mp ? read_pos[r] : mp;
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) {
+        const int32_t o = __shfl_xor(mp, dd, kW);
+        mp = o < mp ? o : mp;
+    }
+    return r1 > r0 ? pos - (int64_t)mp : 0;
+}
+
+// the head of a B:s array of n elements / of a Z string of n characters (and its NUL): returns where
+// the elements start and leaves the writer after the tag
+__device__ __forceinline__ uint32_t tag_arr(Out &w, char a, char b, uint32_t n) {
+    w.tag(a, b, 'B');
+    w.b1('s');
+    w.u32(n);
+    const uint32_t at = w.p;
+    w.p += 2 * n;
+    return at;
+}
+__device__ __forceinline__ uint32_t tag_str(Out &w, char a, char b, uint32_t n) {
+    w.tag(a, b, 'Z');
+    const uint32_t at = w.p;
+    w.p += n;
+    w.b1(0);
+    return at;
+}
+__device__ __forceinline__ void put_s(uint8_t *o, uint32_t at, int64_t i, uint32_t v) {
+    v = v > 32767u ? 32767u : v;
+    o[at + 2 * i] = (uint8_t)v;
+    o[at + 2 * i + 1] = (uint8_t)(v >> 8);
+}
+
+// The records up to and including cQ / sQ, as rec_write / rec_write_ss write
+// them.  Copies, not shared code: the default kernels compile to the parent's
+// instructions only while their own functions stay as they are.
+__device__ void rec_head(const FmtArgs &A, const Rec &r, Out &w, uint32_t total) {
+    const dcr_out &ss = A.ss, &ds = A.ds;
+    uint8_t *o = w.o;
+    w.u32(total - 4);
+    w.u32((uint32_t)r.tid);
+    w.u32((uint32_t)r.pos);
+    w.b1(16 + r.lc + 12 + 1);
+    w.b1((uint32_t)(r.mapq & 0xff));
+    const uint32_t *cg = ds.cigar + r.ro;
+    int64_t rl = 0;
+    if (lane_id() == 0)
+        for (int32_t i = 0; i < r.nc; ++i) {
+            const uint32_t op = cg[i] & 15;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += cg[i] >> 4;
+        }
+    w.u16(r.pos >= 0 ? (uint32_t)reg2bin(r.pos, r.pos + (rl > 0 ? rl : 1)) : 4680u);
+    w.u16((uint32_t)r.nc);
+    w.u16(r.j == 0 ? 99u : 147u);
+    w.u32((uint32_t)r.L);
+    w.u32((uint32_t)r.tid);
+    w.u32((uint32_t)r.opos);
+    w.u32((uint32_t)r.tlen);
+    w.str("consensus_family", 16);
+    w.str(r.code, r.lc);
+    w.str(r.j == 0 ? "_paired-end1" : "_paired-end2", 12);
+    w.b1(0);
+    for (int32_t i = lane_id(); i < r.nc; i += kW) {
+        const uint32_t v = cg[i];
+        for (int b = 0; b < 4; ++b) o[w.p + 4 * i + b] = (uint8_t)(v >> (8 * b));
+    }
+    w.p += 4u * (uint32_t)r.nc;
+    const uint8_t *sq = ds.seq + r.ro;
+    const int32_t nb = (r.L + 1) >> 1;
+    for (int32_t i = lane_id(); i < nb; i += kW) {
+        const uint8_t hi = nt_code(sq[2 * i]);
+        const uint8_t lo = (2 * i + 1 < r.L) ? nt_code(sq[2 * i + 1]) : 0;
+        o[w.p + i] = (uint8_t)((hi << 4) | lo);
+    }
+    w.p += (uint32_t)nb;
+    w.bytes(ds.qual + r.ro, (uint32_t)r.L);
+    w.tag('M', 'I', 'Z');
+    w.str(r.code, r.lc);
+    w.b1(0);
+    w.tag('R', 'X', 'Z');
+    w.str(r.rx, r.lr);
+    w.b1(0);
+    w.tag('a', 'Q', 'B'); w.b1('C'); w.u32((uint32_t)(r.a1 - r.a0)); w.bytes(A.read_mapq + r.a0, (uint32_t)(r.a1 - r.a0));
+    w.tag('b', 'Q', 'B'); w.b1('C'); w.u32((uint32_t)(r.b1 - r.b0)); w.bytes(A.read_mapq + r.b0, (uint32_t)(r.b1 - r.b0));
+    w.tag('c', 'Q', 'B'); w.b1('C'); w.u32(2); w.b1((uint32_t)ss.mapq[r.a] & 0xff); w.b1((uint32_t)ss.mapq[r.b] & 0xff);
+}
+
+__device__ void rec_head_ss(const FmtSsArgs &A, const RecSs &r, Out &w, uint32_t total) {
+    const dcr_out &ss = A.ss;
+    uint8_t *o = w.o;
+    w.u32(total - 4);
+    w.u32((uint32_t)r.tid);
+    w.u32((uint32_t)r.pos);
+    w.b1(16 + r.lc + 3 + 1);
+    w.b1((uint32_t)(r.mapq & 0xff));
+    const uint32_t *cg = ss.cigar + r.ro;
+    int64_t rl = 0;
+    if (lane_id() == 0)
+        for (int32_t i = 0; i < r.nc; ++i) {
+            const uint32_t op = cg[i] & 15;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += cg[i] >> 4;
+        }
+    w.u16(r.pos >= 0 ? (uint32_t)reg2bin(r.pos, r.pos + (rl > 0 ? rl : 1)) : 4680u);
+    w.u16((uint32_t)r.nc);
+    w.u16(A.sub_flag[r.s]);
+    w.u32((uint32_t)r.L);
+    w.u32(0xffffffffu);
+    w.u32(0xffffffffu);
+    w.u32(0);
+    w.str("consensus_family", 16);
+    w.str(r.code, r.lc);
+    const int k = r.s & 3;
+    w.str(k == 0 ? "_A1" : k == 1 ? "_B2" : k == 2 ? "_B1" : "_A2", 3);
+    w.b1(0);
+    for (int32_t i = lane_id(); i < r.nc; i += kW) {
+        const uint32_t v = cg[i];
+        for (int b = 0; b < 4; ++b) o[w.p + 4 * i + b] = (uint8_t)(v >> (8 * b));
+    }
+    w.p += 4u * (uint32_t)r.nc;
+    const uint8_t *sq = ss.seq + r.ro;
+    const int32_t nb = (r.L + 1) >> 1;
+    for (int32_t i = lane_id(); i < nb; i += kW) {
+        const uint8_t hi = nt_code(sq[2 * i]);
+        const uint8_t lo = (2 * i + 1 < r.L) ? nt_code(sq[2 * i + 1]) : 0;
+        o[w.p + i] = (uint8_t)((hi << 4) | lo);
+    }
+    w.p += (uint32_t)nb;
+    w.bytes(ss.qual + r.ro, (uint32_t)r.L);
+    w.tag('M', 'I', 'Z');
+    w.str(r.mi, r.lmi);
+    w.b1(0);
+    w.tag('R', 'X', 'Z');
+    w.str(r.rx, r.lrx);
+    w.b1(0);
+    w.tag('s', 'Q', 'B'); w.b1('C'); w.u32((uint32_t)(r.r1 - r.r0)); w.bytes(A.read_mapq + r.r0, (uint32_t)(r.r1 - r.r0));
+}
+
+__device__ void rec_write_tags(const FmtTagArgs &T, const Rec &r, uint8_t *o, uint32_t total) {
+    const FmtArgs &A = T.f;
+    const dcr_out &ss = A.ss, &ds = A.ds;
+    Out w{o, 0};
+    rec_head(A, r, w, total);
+    const uint32_t L = (uint32_t)r.L;
+    const uint32_t ad = tag_arr(w, 'a', 'd', L), bd = tag_arr(w, 'b', 'd', L), cd = tag_arr(w, 'c', 'd', L);
+    w.int_tag('a', 'D', ss.D[r.a]); w.int_tag('b', 'D', ss.D[r.b]); w.int_tag('c', 'D', ds.D[r.k]);
+    w.int_tag('a', 'M', ss.M[r.a]); w.int_tag('b', 'M', ss.M[r.b]); w.int_tag('c', 'M', ds.M[r.k]);
+    const uint32_t ae = tag_arr(w, 'a', 'e', L), be = tag_arr(w, 'b', 'e', L), ce = tag_arr(w, 'c', 'e', L);
+    w.float_tag('a', 'E', ss.E[r.a]); w.float_tag('b', 'E', ss.E[r.b]); w.float_tag('c', 'E', ds.E[r.k]);
+    const uint32_t ac = tag_str(w, 'a', 'c', L), bc = tag_str(w, 'b', 'c', L);
+    const uint32_t aq = tag_str(w, 'a', 'q', L), bq = tag_str(w, 'b', 'q', L);
+    // the maps of the three records, as k_base_filter sets them up
+    BfRec S[2], R;
+    for (int s = 0; s < 2; ++s) {
+        bf_rec(ss, A.ss_col_off, r.a + s, T.ss_col, T.flag[r.a + s] != 0, S[s]);
+        if (!S[s].mapped) S[s].t5 = tag_t5(A.sub_off, T.read_pos, r.a + s, S[s].pos);
+    }
+    bf_rec(ds, A.ds_col_off, r.k, T.ds_col, T.flag[4 * (int64_t)A.n_fam + r.k] != 0, R);
+    const int64_t minpos = S[0].pos < S[1].pos ? S[0].pos : S[1].pos;
+    R.t5 = R.pos - minpos;
+    const uint32_t *aln = T.ds_aln + r.ro;
+    const bool lane_math = R.simple && S[0].simple && S[1].simple;
+    const uint8_t *sq[2] = {ss.seq + r.ao, ss.seq + r.bo}, *ql[2] = {ss.qual + r.ao, ss.qual + r.bo};
+    const uint32_t at_d[2] = {ad, bd}, at_e[2] = {ae, be}, at_c[2] = {ac, bc}, at_q[2] = {aq, bq};
+    for (int64_t i = lane_id(); i < (int64_t)L; i += kW) {
+        int64_t c = -1, ix[2] = {-1, -1};       // the duplex d-index, the strands' base indices (-1: none)
+        if (i < R.len) {
+            if (lane_math) {
+                c = R.t5 + i;
+                for (int s = 0; s < 2; ++s) {
+                    const int64_t b = minpos + c - S[s].pos;
+                    ix[s] = b >= 0 && b < S[s].len ? b : -1;
+                }
+            } else {
+                int64_t t;
+                if (R.mapped) {
+                    c = (int64_t)R.col[i];
+                    t = (int64_t)aln[i];
+                } else {
+                    c = t = bf_own_col(R, i);   // no '+' column: the d-index is the alignment column
+                }
+                bf_sources(S[0], S[1], minpos, t, ix[0], ix[1]);
+            }
+        }
+        for (int s = 0; s < 2; ++s) {
+            const int64_t cs = bf_own_col(S[s], ix[s]);
+            const bool v = cs >= 0 && cs < S[s].nde;
+            put_s(o, at_d[s], i, v ? S[s].d[cs] : 0u);
+            put_s(o, at_e[s], i, v ? S[s].e[cs] : 0u);
+            o[at_c[s] + i] = ix[s] >= 0 ? sq[s][ix[s]] : (uint8_t)'N';
+            o[at_q[s] + i] = ix[s] >= 0 ? (uint8_t)(ql[s][ix[s]] + 33) : (uint8_t)'!';
+        }
+        const bool vc = c >= 0 && c < R.nde;
+        put_s(o, cd, i, vc ? R.d[c] : 0u);
+        put_s(o, ce, i, vc ? R.e[c] : 0u);
+    }
+}
+
+// one wave per duplex record, as k_fmt_size
+__global__ __launch_bounds__(256) void k_fmt_size_tags(FmtArgs A) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;
+    const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
+    for (int64_t k = wave; k < 2LL * A.n_fam; k += nw) {
+        uint32_t n = 0;
+        if (A.fam_fail[k >> 1] == 0 && !(A.fam_filt && (A.fam_filt[k >> 1] & 0xff))) {
+            Rec r;
+            rec_setup(A, (int32_t)k, r);
+            n = rec_size_tags(A, r);
+        }
+        if (lane_id() == 0) A.rec_size[k] = n;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fmt_write_tags(FmtTagArgs T) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;
+    const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
+    for (int64_t k = wave; k < 2LL * T.f.n_fam; k += nw) {
+        const int64_t o = T.f.rec_off[k], n = T.f.rec_off[k + 1] - o;
+        if (n == 0) continue;
+        Rec r;
+        rec_setup(T.f, (int32_t)k, r);
+        rec_write_tags(T, r, T.f.stream + o, (uint32_t)n);
+    }
+}
+
+// the single-strand records: sd / se per base from the record's own columns (Level 1)
+__device__ uint32_t rec_size_ss_tags(const FmtSsArgs &A, const RecSs &r) {
+    const dcr_out &ss = A.ss;
+    uint32_t n = 36 + 16 + r.lc + 3 + 1 + 4u * (uint32_t)r.nc + (uint32_t)((r.L + 1) >> 1) + (uint32_t)r.L;
+    n += 3 + r.lmi + 1 + 3 + r.lrx + 1;                      // MI, RX
+    n += 8 + (uint32_t)(r.r1 - r.r0);                        // sQ
+    n += 2 * (kTagArr + 2u * (uint32_t)r.L);                 // sd, se
+    n += int_tag_bytes(ss.D[r.s]) + int_tag_bytes(ss.M[r.s]) + 7;
+    return n;
+}
+
+__device__ void rec_write_ss_tags(const FmtSsTagArgs &T, const RecSs &r, uint8_t *o, uint32_t total) {
+    const FmtSsArgs &A = T.f;
+    const dcr_out &ss = A.ss;
+    Out w{o, 0};
+    rec_head_ss(A, r, w, total);
+    const uint32_t L = (uint32_t)r.L;
+    const uint32_t sd = tag_arr(w, 's', 'd', L);
+    w.int_tag('s', 'D', ss.D[r.s]);
+    w.int_tag('s', 'M', ss.M[r.s]);
+    const uint32_t se = tag_arr(w, 's', 'e', L);
+    w.float_tag('s', 'E', ss.E[r.s]);
+    BfRec S;
+    bf_rec(ss, A.ss_col_off, r.s, T.ss_col, T.flag[r.s] != 0, S);
+    if (!S.mapped) S.t5 = tag_t5(A.sub_off, T.read_pos, r.s, S.pos);
+    for (int64_t i = lane_id(); i < (int64_t)L; i += kW) {
+        const int64_t c = bf_own_col(S, i);
+        const bool v = c >= 0 && c < S.nde;
+        put_s(o, sd, i, v ? S.d[c] : 0u);
+        put_s(o, se, i, v ? S.e[c] : 0u);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fmt_size_ss_tags(FmtSsArgs A) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;
+    const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
+    for (int64_t s = wave; s < 4LL * A.n_fam; s += nw) {
+        uint32_t n = 0;
+        if (A.fam_fail[s >> 2] == 0 && !(A.fam_filt && (A.fam_filt[s >> 2] & 0xff))) {
+            RecSs r;
+            rec_setup_ss(A, (int32_t)s, r);
+            n = rec_size_ss_tags(A, r);
+        }
+        if (lane_id() == 0) A.rec_size[s] = n;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fmt_write_ss_tags(FmtSsTagArgs T) {
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kW;
+    const int64_t nw = (int64_t)gridDim.x * blockDim.x / kW;
+    for (int64_t s = wave; s < 4LL * T.f.n_fam; s += nw) {
+        const int64_t o = T.f.rec_off[s], n = T.f.rec_off[s + 1] - o;
+        if (n == 0) continue;
+        RecSs r;
+        rec_setup_ss(T.f, (int32_t)s, r);
+        rec_write_ss_tags(T, r, T.f.stream + o, (uint32_t)n);
     }
 }
 

@@ -220,7 +220,12 @@ class DeviceStream:
 
     ``metrics`` (set per run too): the device writer counts the consensus QC
     tables (dcr_set_metrics) and ``result`` carries them as ``metrics``; on the
-    host path the caller counts (native_io.metrics)."""
+    host path the caller counts (native_io.metrics).
+
+    ``base_tags`` (set per run too, --per_base_tags): the device writer writes
+    the ten per-column tags of the duplex records, and sd / se of the
+    single-strand ones, per base of SEQ (dcr_set_base_tags).  Device writer
+    only, for the per-base rules' reason; the host path ignores it."""
 
     def __init__(self, ctx, n_slots=2, owns_ctx=False, device_writer=True, persistent=False):
         """``persistent``: ``close`` only drains the slots (the context and the
@@ -236,6 +241,7 @@ class DeviceStream:
         self.ss_output = False
         self.filter = None
         self.metrics = False
+        self.base_tags = False
         self.wouts_ss = None
         self.lib = _lib.load()
         self.n_slots = n_slots
@@ -271,9 +277,10 @@ class DeviceStream:
             filtered = self.filter is not None
             counted = bool(self.metrics)
             wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered, counted)
-            # the context may serve other streams: its filter and metrics are this stream's for this batch
+            # the context may serve other streams: its filter, metrics and tags are this stream's for this batch
             self.ctx.set_filter(self.filter)
             self.ctx.set_metrics(counted)
+            self.ctx.set_base_tags(self.base_tags)
             if counted:
                 _lib._check(self.lib.dcr_slot_metrics_out(self.ctx._ctx, slot, wo.met.ptr))
             if filtered:

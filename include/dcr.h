@@ -338,11 +338,45 @@ typedef struct dcr_base_filter {
 } dcr_base_filter;
 /* NULL or active == 0: off (the default; nothing is launched, copied, zeroed
  * or allocated).  Holds for the batches submitted after the call.
- * dcr_slot_fetch what 6 (a batch submitted with a base filter set): one byte
+ * dcr_slot_fetch what 6 (a batch submitted with a base filter set, or with
+ * the per-base tags on, dcr_set_base_tags): one byte
  * per record, single-strand 4F then duplex 2F, 1 where the consensus kernels
  * stored the record's column map (it has insertion columns), 0 where the map
  * follows from pos and CIGAR (diagnostic; the tests read it). */
 int dcr_set_base_filter(dcr_ctx *ctx, const dcr_base_filter *filter);
+
+/* Per-base tags (not a reference feature; the array and string types that
+ * fgbio's FilterConsensusReads / ReviewConsensusVariants and pileup-style
+ * callers expect under these tag names: conformance is to the types stated
+ * here, fgbio itself was not run).  With the tags on, the ten tags ad bd cd ae
+ * be ce ac bc aq bq of every duplex record dcr_submit_write[_ss] writes keep
+ * their names and their places in the tag order and carry one value per base
+ * of the record's seq, in seq order, instead of one per alignment column.
+ * Levels 1 and 2 are the per-base filters' above.  For duplex record
+ * r = 2f + j, called from a = 4f + 2j and b = a + 1, and base i of its seq
+ * (len bases): c = col_r(i); (ia, ib) the strands' base indices in that
+ * alignment column; ca = col_a(ia), cb = col_b(ib).
+ *   ad ae bd be  B:s, len entries: ad[i] = min(ss.d[a][ca], 32767), ae[i] =
+ *                min(ss.e[a][ca], 32767), both 0 when strand a has no base in
+ *                the column; bd be the same for strand b
+ *   cd ce        B:s, len entries: cd[i] = min(ds.d[r][c], 32767), ce likewise
+ *   ac bc        Z of exactly len characters: ac[i] = ss.seq[a][ia], or 'N'
+ *                when strand a has no base there
+ *   aq bq        Z of exactly len characters: aq[i] = chr(ss.qual[a][ia] + 33),
+ *                or '!' (a written family has no strand quality >= 95: the
+ *                reference fails it at :1384, fam_fail says so)
+ * Every other field and tag of the record (MI RX aQ bQ cQ, aD..cE, name, flag,
+ * CIGAR, SEQ, QUAL) is byte for byte what it is without the tags.  Of the
+ * single-strand records s (dcr_submit_write_ss), sd and se become B:s of len
+ * entries, sd[i] = min(ss.d[s][col_s(i)], 32767) and se likewise (Level 1
+ * only); MI RX sQ sD sM sE do not change.  The tags describe the consensus as
+ * called: no filter touches ss.*, ds.d, ds.e or the maps, so a masked base
+ * keeps its values; dropped and failing families write nothing, as without.
+ * Every index is clamped to its record's region before use.
+ * on != 0: on; 0: off (the default; nothing else is launched, copied, zeroed
+ * or allocated and no output byte changes).  Holds for the batches submitted
+ * after the call.  dcr_slot_fetch what 6 serves such a batch too. */
+int dcr_set_base_tags(dcr_ctx *ctx, int on);
 
 /* Consensus QC tables (not a reference feature; what fgbio's
  * CollectDuplexSeqMetrics / ErrorRateByReadPosition read off the written
