@@ -52,6 +52,8 @@ EXPORTS = {
     "dcr_set_base_tags": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "dcr_set_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "dcr_slot_metrics_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "dcr_set_base_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "dcr_slot_base_metrics_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     # include/dcr_inflate.h: BGZF inflate on the device
     "dcr_inflater_create": (ctypes.c_void_p, [ctypes.c_int]),
     "dcr_inflater_destroy": (None, [ctypes.c_void_p]),
@@ -129,6 +131,7 @@ class Context:
         self.filter = None
         self.metrics = False
         self.base_tags = False
+        self.base_metrics = False
         if want_info:
             _check(lib.dcr_set_options(self._ctx, 1))
 
@@ -175,6 +178,15 @@ class Context:
             return
         _check(load().dcr_set_base_tags(self._ctx, 1 if on else 0))
         self.base_tags = bool(on)
+
+    def set_base_metrics(self, on):
+        """The device writer counts the per-base duplex QC tables
+        (dcr_base_metrics) for the batches it takes from now on, or not
+        (dcr_set_base_metrics)."""
+        if bool(on) == self.base_metrics:
+            return
+        _check(load().dcr_set_base_metrics(self._ctx, 1 if on else 0))
+        self.base_metrics = bool(on)
 
     @property
     def stream(self):

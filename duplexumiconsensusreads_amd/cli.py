@@ -32,6 +32,13 @@ tables (include/dcr.h ``dcr_metrics``): family sizes, strand depths, error
 rates, base qualities and errors by read position of the consensus as called,
 before any filter; counted on the device beside the writer.  Off by default.
 
+``--base_metrics_output FILE.json`` (not a reference flag) writes the per-base
+duplex QC tables (include/dcr.h ``dcr_base_metrics``): which strand called which
+base, the strands' depths and error rates per base, qualities by agreement and
+all of it by cycle, of the consensus as called, before any filter; counted on
+the device over the per-base filters' column maps (device writer only).  Off
+by default.
+
 ``--per_base_tags`` (not a reference flag) writes the depth, error and strand
 tags ``ad bd cd ae be ce ac bc aq bq`` (and ``sd se`` of the single-strand
 reads) with one value per base of ``SEQ``, as ``B:s`` arrays and strings of the
@@ -136,6 +143,11 @@ def parse_args(argv):
     ap.add_argument("--metrics_output", required=False, default=None, type=str, metavar="FILE.json",
                     help="count family sizes, strand depths, error rates, qualities and errors by read position "
                          "of the consensus reads as called (before any --filter_*) into FILE.json")
+    # not a reference flag: the per-base duplex QC tables (include/dcr.h dcr_base_metrics) as JSON
+    ap.add_argument("--base_metrics_output", required=False, default=None, type=str, metavar="FILE.json",
+                    help="count, per base of the duplex consensus reads as called (before any --filter_*), the "
+                         "strands' calls against each other, their depths and error rates, the qualities by "
+                         "agreement and all of it by cycle into FILE.json")
     # not a reference flag: the per-column tags per base of SEQ (include/dcr.h dcr_set_base_tags)
     ap.add_argument("--per_base_tags", action="store_true",
                     help="write ad bd cd ae be ce as B:s arrays and ac bc aq bq as strings with one value per base "
@@ -282,12 +294,14 @@ def gpu_inflate(device: int = 0):
     return got[0]
 
 
-def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=False, base_tags=False):
+def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=False, base_tags=False,
+                base_metrics=False):
     """``ss_output``: this run also writes the single-strand records (a
     property of the run, set on the backend each time: the default backend
     is kept across runs).  ``flt``: this run's ConsensusFilter or None,
-    set each time in the same way; so are ``metrics`` (--metrics_output) and
-    ``base_tags`` (--per_base_tags)."""
+    set each time in the same way; so are ``metrics`` (--metrics_output),
+    ``base_tags`` (--per_base_tags) and ``base_metrics``
+    (--base_metrics_output)."""
     if backend is None:
         be = default_backend(params, device)
     elif hasattr(backend, "submit"):
@@ -315,6 +329,11 @@ def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=Fa
         raise ValueError("this backend cannot write the per-base tags")
     if hasattr(be, "base_tags"):
         be.base_tags = base_tags
+    if base_metrics and not getattr(be, "device_writer", False):
+        # no host path, for the tags' reason
+        raise ValueError("this backend cannot count the per-base metrics")
+    if hasattr(be, "base_metrics"):
+        be.base_metrics = base_metrics
     return be
 
 
@@ -331,26 +350,37 @@ def _check_ss_output(args, say=True):
 
 
 def _check_metrics_output(args, say=True):
-    """--metrics_output must name a .json file; it is created here, before
-    the pass and before any output file, so a bad path fails early."""
-    path = args.metrics_output
-    if path is None:
-        return
-    if not path.endswith(".json"):
-        if say:
-            print(OUTPUT_FORMAT_ERROR)
-        raise ReferenceExit(1)
-    open(path, "a").close()
+    """--metrics_output and --base_metrics_output must name .json files; they
+    are created here, before the pass and before any output file, so a bad
+    path fails early."""
+    paths = [p for p in (args.metrics_output, args.base_metrics_output) if p is not None]
+    for path in paths:
+        if not path.endswith(".json"):
+            if say:
+                print(OUTPUT_FORMAT_ERROR)
+            raise ReferenceExit(1)
+    made = []
+    try:
+        for path in paths:
+            open(path, "a").close()
+            made.append(path)
+    except BaseException:
+        for path in made:               # neither file from a run that never starts
+            with contextlib.suppress(OSError):
+                os.remove(path)
+        raise
 
 
-def _finish_metrics(path, total, done):
+def _finish_metrics(path, total, done, to_json=None):
     """The run's counters as JSON when it completed; otherwise no file (the
-    counters of the families after a failing one cannot be separated out)."""
+    counters of the families after a failing one cannot be separated out).
+    ``to_json``: params.metrics_json, or base_metrics_json for
+    --base_metrics_output."""
     if path is None:
         return
     if done and total is not None:
         with open(path, "w") as f:
-            f.write(params_mod.metrics_json(total))
+            f.write((to_json or params_mod.metrics_json)(total))
     else:
         with contextlib.suppress(OSError):
             os.remove(path)
@@ -385,6 +415,8 @@ class _Driver:
             self.stats.update(filter_dropped_families=0, filter_masked_bases=0)
         # --metrics_output: the batches' counters summed at once (a device slot's block is overwritten on reuse)
         self.metrics_total = np.zeros(params_mod.MET_WORDS, np.uint64) if args.metrics_output is not None else None
+        self.base_metrics_total = (np.zeros(params_mod.BMET_WORDS, np.uint64)
+                                   if args.base_metrics_output is not None else None)
 
     # -- stdout of one batch, in the reference's order --------------------------
     def _prints(self, hb, fail_f, kind, which, last_batch):
@@ -527,6 +559,8 @@ class _Driver:
             filt = res.fam_filt[:fail_f] if self.filter is not None else None
             if self.metrics_total is not None:
                 self.metrics_total += res.metrics
+            if self.base_metrics_total is not None:
+                self.base_metrics_total += res.base_metrics
         else:
             ss, ds, rstat = res
             fail_f, kind, which = native_io.first_failure(hb, ss, ds, F, rstat)
@@ -721,22 +755,24 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
         ing.close()
         raise
     met_path, met_total, done = args.metrics_output, None, False
+    bmet_path, bmet_total = args.base_metrics_output, None
     try:
         be = _as_backend(backend, params, args.device, ss_path is not None, ConsensusFilter.from_args(args),
-                         met_path is not None, args.per_base_tags)
+                         met_path is not None, args.per_base_tags, bmet_path is not None)
         cons, excl, unproc, *rest = _open_writers(
             [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
              "%s_filteredfamilies.bam" % consensus_filename[:-4]] + ([ss_path] if ss_path else []), ing.header, args,
             ing)
     except BaseException:
         _finish_metrics(met_path, None, False)      # no empty metrics file from a run that never started
+        _finish_metrics(bmet_path, None, False)
         raise
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng.getstate())
     t_open = time.perf_counter()
     try:
         drv = _Driver(args, params, be, ing, cons, excl, unproc, sscs)
-        met_total = drv.metrics_total
+        met_total, bmet_total = drv.metrics_total, drv.base_metrics_total
         if stats is not None and "trace" in stats:
             drv.trace = stats["trace"]
         try:
@@ -766,7 +802,10 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
                 try:
                     ing.close()
                 finally:
-                    _finish_metrics(met_path, met_total, done)
+                    try:
+                        _finish_metrics(met_path, met_total, done)
+                    finally:
+                        _finish_metrics(bmet_path, bmet_total, done, params_mod.base_metrics_json)
         if stats is not None:
             stats["close_s"] = time.perf_counter() - t_close
             stats["close_writers_s"] = t_wclose - t_close
@@ -923,7 +962,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
                            params.min_base_quality, args.threads, rng_range[0], rng_range[1],
                            ss_meta=len(parts) > 3)
     be = _as_backend(backend, params, device, len(parts) > 3, ConsensusFilter.from_args(args),
-                     args.metrics_output is not None, args.per_base_tags)
+                     args.metrics_output is not None, args.per_base_tags, args.base_metrics_output is not None)
     cons, excl, unproc, *rest = _open_writers(parts, header, args, ing)
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng_state)
@@ -944,6 +983,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
         res["calls"] = ing.sample_calls()
         res["counters"] = dict(ing.counters(), **drv.filter_counts)
         res["metrics"] = drv.metrics_total
+        res["base_metrics"] = drv.base_metrics_total
         res["stats"] = dict(drv.stats)
         res["stdout"] = out.getvalue()
         try:
@@ -1344,8 +1384,15 @@ def _main_sharded(args, params, backend, rng, stats, group):
                 if results[r].get("metrics") is not None:
                     met += results[r]["metrics"]
             _finish_metrics(args.metrics_output, met, True)
+        if args.base_metrics_output is not None:
+            bmet = np.zeros(params_mod.BMET_WORDS, np.uint64)
+            for r in range(min(world, len(ranges))):
+                if results[r].get("base_metrics") is not None:
+                    bmet += results[r]["base_metrics"]
+            _finish_metrics(args.base_metrics_output, bmet, True, params_mod.base_metrics_json)
         return 0
     _finish_metrics(args.metrics_output, None, False)
+    _finish_metrics(args.base_metrics_output, None, False)
     st, ea = results[fail]["status"], results[fail]["exc_args"]
     if st == "exit":
         raise ReferenceExit(*ea)

@@ -224,6 +224,7 @@ struct WriterBufs {
     // null unless a base filter or the per-base tags (dcr_set_base_tags) are on: the column maps
     // k_consensus_general_map stores for them
     dcr::BaseMap bmap;
+    dcr_base_metrics *base_metrics;   // k_base_metrics' accumulator; null unless base metrics are on (dcr_set_base_metrics)
 };
 
 // The second stream of dcr_submit_write_ss: the single-strand records'
@@ -266,11 +267,12 @@ void plan_writer_ss(int64_t F, Plan &p, WriterSsBufs &ws) {
 // and with filt, k_filter's outcomes (no region without it); with met,
 // k_metrics' accumulator (none without it); with bfilt (a base filter is set)
 // k_base_filter's counts and with maps (the batch, when a base filter or the
-// per-base tags are on) the column maps, after every other region (none
-// without them)
+// per-base tags or the base metrics are on) the column maps, after every
+// other region (none without them); with bmet, k_base_metrics' accumulator
+// after those
 void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w,
                  WriterSsBufs *ws = nullptr, bool filt = false, bool met = false, const dcr_batch *maps = nullptr,
-                 bool bfilt = false) {
+                 bool bfilt = false, bool bmet = false) {
     w.names = p.take<char>((size_t)n_names + 1);
     w.fam_code = p.take<int64_t>((size_t)F);
     w.fam_rx = p.take<int64_t>(2 * (size_t)F);
@@ -299,6 +301,7 @@ void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd
         w.bmap.ds_col = p.take<uint32_t>((size_t)maps->ds_cols);
         w.bmap.ds_aln = p.take<uint32_t>((size_t)maps->ds_cols);
     }
+    w.base_metrics = bmet ? p.take<dcr_base_metrics>(1) : nullptr;
 }
 }  // namespace
 
@@ -337,13 +340,14 @@ struct dcr_ctx {
         // the single-strand stream of dcr_submit_write_ss (writer_ss)
         int64_t *d_ss_rec_off = nullptr;
         uint8_t *d_ss_stream = nullptr, *d_ss_comp = nullptr;
-        uint8_t *d_map_flag = nullptr;   // the batch's BaseMap::flag when a base filter or base tags were on, else null
+        uint8_t *d_map_flag = nullptr;   // the batch's BaseMap::flag when the column maps were made, else null
         int64_t n_fam = 0;
         bool writer = false, writer_ss = false;
         hipEvent_t ev_h2d = nullptr, ev_comp = nullptr, ev_d2h = nullptr;
         int *h_err = nullptr;     // pinned copy of the batch's capacity flag
         int32_t *h_fam_filt = nullptr;   // the caller's pinned fam_filt (dcr_slot_filter_out), or null
         dcr_metrics *h_metrics = nullptr;   // the caller's pinned counters (dcr_slot_metrics_out), or null
+        dcr_base_metrics *h_base_metrics = nullptr;   // the same for dcr_slot_base_metrics_out
         bool busy = false;
     } slots[DCR_MAX_SLOTS];
     dcr::Workspace w{};
@@ -357,8 +361,9 @@ struct dcr_ctx {
     bool metrics = false;   // dcr_set_metrics
     dcr_base_filter base_filter{};   // dcr_set_base_filter; active == 0: off
     bool base_tags = false;          // dcr_set_base_tags
+    bool base_metrics = false;       // dcr_set_base_metrics
     // the column maps of the batch being submitted (submit_write sets them around its
-    // dcr_run_batch when a base filter or the per-base tags are on); all null otherwise
+    // dcr_run_batch when a base filter, the per-base tags or the base metrics are on); all null otherwise
     dcr::BaseMap bmap{};
     // fast-kernel constants (fast_constants)
     uint32_t fast_kq = 0, fast_kqlo = 0;
@@ -612,7 +617,7 @@ static int launch_strand(dcr_ctx *c, dcr::Args &a, const dcr_batch *in, const dc
     // after k_decide_deep: it reads the general list's entries, which
     // k_ins_layout marks decided (bit 31) for the records it decides
     hipLaunchKernelGGL(dcr::k_ins_layout<DUPLEX>, dim3(grid_for(2048)), dim3(256), 0, c->stream, a);
-    // with a base filter or the per-base tags on, the instantiation that also stores the base maps
+    // with a base filter, the per-base tags or the base metrics on, the instantiation that also stores the base maps
     if (c->bmap.flag)
         hipLaunchKernelGGL(dcr::k_consensus_general_map<DUPLEX>, dim3(grid_for(1024)), dim3(256), 0, c->stream, a, c->bmap);
     else
@@ -1063,17 +1068,20 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     // a base filter alone still gives fam_filt: k_filter runs to add the masked counts into it
     const bool bfilt = c->base_filter.active != 0;
     const bool filt = c->filter.active != 0 || bfilt;
-    const bool maps = bfilt || btags;       // the column maps: planned, zeroed and filled for either
+    const bool bmet = c->base_metrics;
+    const bool maps = bfilt || btags || bmet;   // the column maps: planned, zeroed and filled for any of them
     if (filt && F && !S.h_fam_filt)
         return fail(DCR_EARG, "a filter is set but the slot has no fam_filt destination (dcr_slot_filter_out)");
     const bool met = c->metrics;
     if (met && !S.h_metrics)
         return fail(DCR_EARG, "metrics are on but the slot has no destination (dcr_slot_metrics_out)");
+    if (bmet && !S.h_base_metrics)
+        return fail(DCR_EARG, "base metrics are on but the slot has no destination (dcr_slot_base_metrics_out)");
     Plan wsz;
-    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt);
+    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt, bmet);
     if (wsz.off > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wsz.off + wsz.off / 8));
     Plan wp{(char *)S.wbuf.p};
-    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt);
+    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt, bmet);
     // H2D: inputs and writer metadata on the copy stream
     HIP_TRY(upload_inputs(h, db, c->s_h2d));
     if (m->n_names) HIP_TRY(hipMemcpyAsync(wb.names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
@@ -1087,8 +1095,8 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         HIP_TRY(hipMemcpyAsync(wsb.sub_mi, ms->sub_mi, 32 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
         HIP_TRY(hipMemcpyAsync(wsb.sub_rx, ms->sub_rx, 32 * (size_t)F, hipMemcpyHostToDevice, c->s_h2d));
     }
-    // with a base filter or the per-base tags the general kernels store the column maps of the
-    // records with insertion columns and flag them; the flags start from zero for every batch
+    // with a base filter, the per-base tags or the base metrics the general kernels store the column maps
+    // of the records with insertion columns and flag them; the flags start from zero for every batch
     if (maps && F) HIP_TRY(hipMemsetAsync(wb.bmap.flag, 0, 6 * (size_t)F, c->stream));
     c->bmap = wb.bmap;
     rc = slot_run(c, S, h, &db, dout);
@@ -1118,6 +1126,7 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     HIP_TRY(hipMemsetAsync(wb.bsz, 0, 8 * (size_t)(nbm + 2), c->stream));
     // the slot's counters start from zero for every batch (an empty batch gives zeros)
     if (met) HIP_TRY(hipMemsetAsync(wb.metrics, 0, sizeof(dcr_metrics), c->stream));
+    if (bmet) HIP_TRY(hipMemsetAsync(wb.base_metrics, 0, sizeof(dcr_base_metrics), c->stream));
     if (F) {
         hipLaunchKernelGGL(dcrw::k_famfail, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, c->stream, A);
         if (met) {
@@ -1128,6 +1137,36 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
             const int wpg = dcrw::kMetThreads / 64;
             const unsigned gm = (unsigned)std::max<int64_t>(1, std::min<int64_t>((F + wpg - 1) / wpg, (int64_t)c->n_cu));
             hipLaunchKernelGGL(dcrw::k_metrics, dim3(gm), dim3(dcrw::kMetThreads), 0, c->stream, Ma);
+        }
+        if (bmet) {
+            // one wave per duplex record, after k_metrics and before the filters mask the duplex seq /
+            // qual; at most one workgroup per CU: every workgroup ends with a global add per non-zero
+            // bin.  A launch's 32-bit LDS bins take one per base: families are launched in ranges whose
+            // duplex regions (which bound len, itself an int32) hold fewer than 2^32 columns, one range
+            // for every batch but an enormous one
+            dcrw::BaseMetricsArgs Ba{dout[0], dout[1], db.sub_off, db.read_pos, db.ss_col_off, db.ds_col_off,
+                                     wb.fam_fail, wb.bmap.ss_col, wb.bmap.ds_col, wb.bmap.ds_aln, wb.bmap.flag,
+                                     (int32_t)F, 0, 0, wb.base_metrics};
+            const int wpg = dcrw::kBmThreads / 64;
+            const int64_t lim = (int64_t)1 << 32, rmax = 0x7fffffff;
+            for (int64_t f0 = 0; f0 < F;) {
+                int64_t f1 = F;
+                if (h->ds_cols >= lim) {
+                    int64_t cols = 0;
+                    for (f1 = f0; f1 < F; ++f1) {
+                        const int64_t n = std::min(h->ds_col_off[2 * f1 + 1] - h->ds_col_off[2 * f1], rmax) +
+                                          std::min(h->ds_col_off[2 * f1 + 2] - h->ds_col_off[2 * f1 + 1], rmax);
+                        if (cols + n >= lim) break;
+                        cols += n;
+                    }
+                }
+                Ba.f0 = (int32_t)f0;
+                Ba.f1 = (int32_t)f1;
+                const unsigned gb = (unsigned)std::max<int64_t>(
+                    1, std::min<int64_t>((2 * (f1 - f0) + wpg - 1) / wpg, (int64_t)c->n_cu));
+                hipLaunchKernelGGL(dcrw::k_base_metrics, dim3(gb), dim3(dcrw::kBmThreads), 0, c->stream, Ba);
+                f0 = f1;
+            }
         }
         if (filt) {
             // one wave per family, before anything reads the duplex seq / qual
@@ -1231,6 +1270,9 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         if (filt) HIP_TRY(hipMemcpyAsync(S.h_fam_filt, wb.fam_filt, 4 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
     }
     if (met) HIP_TRY(hipMemcpyAsync(S.h_metrics, wb.metrics, sizeof(dcr_metrics), hipMemcpyDeviceToHost, c->s_d2h));
+    if (bmet)
+        HIP_TRY(hipMemcpyAsync(S.h_base_metrics, wb.base_metrics, sizeof(dcr_base_metrics), hipMemcpyDeviceToHost,
+                               c->s_d2h));
     HIP_TRY(hipMemcpyAsync(res->totals, wb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
     if (ms) HIP_TRY(hipMemcpyAsync(res_ss->totals, wsb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
     HIP_TRY(hipEventRecord(S.ev_d2h, c->s_d2h));
@@ -1302,6 +1344,19 @@ int dcr_set_metrics(dcr_ctx *c, int on) {
 int dcr_set_base_tags(dcr_ctx *c, int on) {
     if (!c) return fail(DCR_EARG, "NULL context");
     c->base_tags = on != 0;
+    return DCR_OK;
+}
+
+int dcr_set_base_metrics(dcr_ctx *c, int on) {
+    if (!c) return fail(DCR_EARG, "NULL context");
+    c->base_metrics = on != 0;
+    return DCR_OK;
+}
+
+int dcr_slot_base_metrics_out(dcr_ctx *c, int slot, dcr_base_metrics *pinned_dst) {
+    if (!c || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
+    if (c->slots[slot].busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
+    c->slots[slot].h_base_metrics = pinned_dst;
     return DCR_OK;
 }
 
@@ -1389,7 +1444,7 @@ int dcr_slot_fetch(dcr_ctx *c, int slot, int what, int64_t off, int64_t n, void 
             if (n) HIP_TRY(hipMemcpy(dst, S.d_ss_comp + off, (size_t)n, hipMemcpyDeviceToHost));
         }
     } else if (what == 6) {
-        if (!S.d_map_flag) return fail(DCR_EARG, "slot's batch ran without a base filter or the per-base tags");
+        if (!S.d_map_flag) return fail(DCR_EARG, "slot's batch ran without a base filter, the per-base tags or the base metrics");
         if (off + n > 6 * S.n_fam) return fail(DCR_EARG, "map flags out of range");
         if (n) HIP_TRY(hipMemcpy(dst, S.d_map_flag + off, (size_t)n, hipMemcpyDeviceToHost));
     } else {

@@ -99,6 +99,22 @@ struct FmtSsTagArgs {
     const uint8_t *flag;            // [6F]: the single-strand records' are the first 4F
 };
 
+// the per-base duplex QC tables (k_base_metrics, dcr_set_base_metrics): what the column of a base
+// needs (as BaseFilterArgs), everything read only
+struct BaseMetricsArgs {
+    dcr_out ss, ds;                 // device kernel outputs (before the filters mask ds)
+    const int32_t *sub_off;         // [4F+1]
+    const int32_t *read_pos;        // [n_reads]
+    const int64_t *ss_col_off, *ds_col_off;
+    const int32_t *fam_fail;        // [F] from k_famfail
+    const uint32_t *ss_col, *ds_col, *ds_aln;   // the stored maps (dcr::BaseMap)
+    const uint8_t *flag;            // [6F]
+    int32_t n_fam;
+    int32_t f0, f1;                 // the families of this launch: their duplex regions hold fewer than 2^32 columns
+    dcr_base_metrics *out;          // the slot's accumulator, zeroed before the first launch
+};
+constexpr int kBmThreads = 1024;    // k_base_metrics' workgroup: 16 waves on one set of LDS tables
+
 struct DflArgs {
     const uint8_t *stream;
     const int64_t *stream_bytes;    // device scalar (rec_off[2F])
@@ -130,6 +146,7 @@ __global__ void k_fmt_size_tags(FmtArgs A);
 __global__ void k_fmt_write_tags(FmtTagArgs T);
 __global__ void k_fmt_size_ss_tags(FmtSsArgs A);
 __global__ void k_fmt_write_ss_tags(FmtSsTagArgs T);
+__global__ void k_base_metrics(BaseMetricsArgs A);
 __global__ void k_deflate(DflArgs D);
 __global__ void k_compact(CompactArgs C);
 

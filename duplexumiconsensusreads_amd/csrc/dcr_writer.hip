@@ -7,7 +7,8 @@
 // set (dcr_set_filter) k_filter first, which masks weak duplex bases and marks
 // the families neither stream writes.  With the per-base tags on
 // (dcr_set_base_tags) kernels of their own format both streams, the default
-// ones staying as they are.
+// ones staying as they are.  With the per-base QC tables on
+// (dcr_set_base_metrics) k_base_metrics counts over the same maps.
 //
 // Reference (/root/reference/DuplexUMIConsensusReads.py): record fields
 // make_consensus_read :1352-1384, names / flags :892-968, duplex tags
@@ -1295,6 +1296,209 @@ __global__ __launch_bounds__(256) void k_fmt_write_ss_tags(FmtSsTagArgs T) {
         RecSs r;
         rec_setup_ss(T.f, (int32_t)s, r);
         rec_write_ss_tags(T, r, T.f.stream + o, (uint32_t)n);
+    }
+}
+
+// ---- the per-base duplex QC tables (dcr_set_base_metrics; include/dcr.h
+// states them).  One wave per duplex record, 64 bases at a time; every lane
+// finds the columns and source bases of its own base exactly as
+// rec_write_tags does (bf_rec, tag_t5, the single M run shortcut, the stored
+// maps of the records that have them, else bf_own_col + bf_sources) and then
+// counts instead of storing.  Nothing per base goes to HBM (a same-address
+// device atomic costs about 30 ns serialised; a batch has millions of bases in
+// a few hundred bins).  Three levels, in the shape of k_metrics:
+//   wave    the loop over a record is uniform (every lane stays in it, the
+//           ones past the end inactive), so the scalars n[] are popcounts of
+//           ballots kept in scalar registers, and for pair, depth, err and
+//           qual the lanes that share the first active lane's bin (the hot
+//           bin: most bases agree at one quality, one depth pair and err[0])
+//           are added by one lane with one LDS add (bm_count); the other
+//           lanes add their own.  The cycle bins of 64 consecutive bases are
+//           64 different addresses; a whole step past bin 511 is summed over
+//           the wave and added once;
+//   LDS     the workgroup's copy of dcr_base_metrics: 32-bit for the count
+//           tables, 64-bit for n[] and the two sums of cyc (what 4, 5);
+//   HBM     at the end one global 64-bit add per non-zero bin per workgroup.
+// No counter wraps: every 32-bit LDS bin takes at most 1 per base, and a
+// launch covers families [f0, f1) whose duplex regions hold fewer than 2^32
+// columns (len is clamped to the region; the host splits a larger batch into
+// several launches, which is the bounded flush); the sums are 64-bit, a
+// step's wave sum of s or e is at most 64 * 2 * 65535; n[] is 64-bit.
+// Every index is clamped to its region (bf_rec).
+constexpr int kBmWords = (int)(sizeof(dcr_base_metrics) / 8);
+constexpr int kBmPair = (int)(offsetof(dcr_base_metrics, pair) / 8);
+constexpr int kBmDepth = (int)(offsetof(dcr_base_metrics, depth) / 8) - kBmPair;
+constexpr int kBmErr = (int)(offsetof(dcr_base_metrics, err) / 8) - kBmPair;
+constexpr int kBmQual = (int)(offsetof(dcr_base_metrics, qual) / 8) - kBmPair;
+constexpr int kBmCyc = (int)(offsetof(dcr_base_metrics, cyc) / 8);
+static_assert(sizeof(dcr_base_metrics) % 8 == 0 && offsetof(dcr_base_metrics, n) == 0 && kBmPair == 8 &&
+                  kBmWords == kBmCyc + 2 * 6 * DCR_BMET_CYC_BINS,
+              "k_base_metrics' LDS layout follows dcr_base_metrics");
+
+struct BmShared {
+    unsigned long long n[8];
+    unsigned long long sum[2][2][DCR_BMET_CYC_BINS];    // cyc what 4, 5
+    uint32_t cnt[kBmCyc - kBmPair];                     // pair, depth, err, qual
+    uint32_t cyc[2][4][DCR_BMET_CYC_BINS];              // cyc what 0 .. 3
+};
+
+__device__ __forceinline__ int bm_code(uint8_t c) {
+    switch (c | 0x20) {
+        case 'a': return 0; case 'c': return 1; case 'g': return 2; case 't': return 3;
+        default: return 4;
+    }
+}
+
+// +1 into h[bin] for the lanes with act (every lane of the wave calls): the lanes that share the
+// first such lane's bin are added by one lane
+__device__ __forceinline__ void bm_count(uint32_t *h, int bin, bool act) {
+    const unsigned long long ma = __ballot(act);
+    if (ma == 0) return;
+    const int b0 = __shfl(bin, (int)__builtin_ctzll(ma), kW);
+    const bool hot = act && bin == b0;
+    const unsigned long long mh = __ballot(hot);
+    if (hot) {
+        if (lane_id() == (int)__builtin_ctzll(mh)) atomicAdd(&h[b0], (uint32_t)__builtin_popcountll(mh));
+    } else if (act) {
+        atomicAdd(&h[bin], 1u);
+    }
+}
+
+__device__ __forceinline__ unsigned long long bm_pop(bool p) {
+    return (unsigned long long)__builtin_popcountll(__ballot(p));
+}
+
+// duplex record k: n[] is the wave's own (the same in every lane)
+__device__ void bm_record(const BaseMetricsArgs &A, BmShared &Sh, int64_t k, unsigned long long (&n)[8]) {
+    const dcr_out &ss = A.ss, &ds = A.ds;
+    const int j = (int)(k & 1);
+    const int64_t a = 4 * (k >> 1) + 2 * j;
+    // the maps of the three records, as rec_write_tags sets them up
+    BfRec S[2], R;
+    for (int s = 0; s < 2; ++s) {
+        bf_rec(ss, A.ss_col_off, a + s, A.ss_col, A.flag[a + s] != 0, S[s]);
+        if (!S[s].mapped) S[s].t5 = tag_t5(A.sub_off, A.read_pos, a + s, S[s].pos);
+    }
+    bf_rec(ds, A.ds_col_off, k, A.ds_col, A.flag[4 * (int64_t)A.n_fam + k] != 0, R);
+    const int64_t minpos = S[0].pos < S[1].pos ? S[0].pos : S[1].pos;
+    R.t5 = R.pos - minpos;
+    const int64_t ro = A.ds_col_off[k];
+    const uint32_t *aln = A.ds_aln + ro;
+    const bool lane_math = R.simple && S[0].simple && S[1].simple;
+    const uint8_t *sq[2] = {ss.seq + A.ss_col_off[a], ss.seq + A.ss_col_off[a + 1]};
+    const uint8_t *dsq = ds.seq + ro, *dql = ds.qual + ro;
+    const int L = __builtin_amdgcn_readfirstlane((int)R.len);      // len is an int32: the clamped value fits
+    n[0] += 1;
+    n[1] += (unsigned long long)L;
+    for (int i0 = 0; i0 < L; i0 += kW) {
+        const int64_t i = (int64_t)i0 + lane_id();
+        const bool act = i < (int64_t)L;
+        int64_t c = -1, ix[2] = {-1, -1};       // the duplex d-index, the strands' base indices (-1: none)
+        if (act) {
+            if (lane_math) {
+                c = R.t5 + i;
+                for (int s = 0; s < 2; ++s) {
+                    const int64_t b = minpos + c - S[s].pos;
+                    ix[s] = b >= 0 && b < S[s].len ? b : -1;
+                }
+            } else {
+                int64_t t;
+                if (R.mapped) {
+                    c = (int64_t)R.col[i];
+                    t = (int64_t)aln[i];
+                } else {
+                    c = t = bf_own_col(R, i);   // no '+' column: the d-index is the alignment column
+                }
+                bf_sources(S[0], S[1], minpos, t, ix[0], ix[1]);
+            }
+        }
+        uint32_t D[2], E[2];
+        int code[2];
+        for (int s = 0; s < 2; ++s) {
+            const int64_t cs = bf_own_col(S[s], ix[s]);
+            const bool v = cs >= 0 && cs < S[s].nde;
+            D[s] = v ? S[s].d[cs] : 0u;
+            E[s] = v ? S[s].e[cs] : 0u;
+            code[s] = ix[s] >= 0 ? bm_code(sq[s][ix[s]]) : 4;
+        }
+        const uint32_t cE = (c >= 0 && c < R.nde) ? R.e[c] : 0u;
+        const bool pa = ix[0] >= 0, pb = ix[1] >= 0, both = pa && pb;
+        const int cls = both ? (code[0] == code[1] ? 0 : 1) : 2;
+        const uint32_t sd = D[0] + D[1], se = E[0] + E[1];
+        const uint32_t q = act ? dql[i] : 0u;
+        const bool isn = act && dsq[i] == (uint8_t)'N';
+        n[2] += bm_pop(act && both);
+        n[3] += bm_pop(act && pa && !pb);
+        n[4] += bm_pop(act && !pa && pb);
+        n[5] += bm_pop(act && !pa && !pb);
+        n[6] += bm_pop(act && cls == 1);
+        n[7] += bm_pop(act && cE > 0);
+        const uint32_t hi = D[0] > D[1] ? D[0] : D[1], lo = D[0] > D[1] ? D[1] : D[0];
+        const int dbin = (int)(hi < 63u ? hi : 63u) * DCR_BMET_DEPTH_BINS + (int)(lo < 63u ? lo : 63u);
+        // s <= 2 * 65535: 1000 * e fits 32 bits whenever e <= s
+        const int ebin = (sd > 0 && se <= sd) ? (se == 0 ? 0 : (int)(1000u * se / sd)) : DCR_BMET_ERR_BINS - 1;
+        bm_count(Sh.cnt, j * 25 + code[0] * 5 + code[1], act && both);      // pair comes first
+        bm_count(Sh.cnt + kBmDepth, dbin, act);
+        bm_count(Sh.cnt + kBmErr, ebin, act);
+        bm_count(Sh.cnt + kBmQual, cls * DCR_BMET_QUAL_BINS + (int)q, act);
+        // the cycle: i' from the sequencing 5' end
+        const int last = i0 + kW - 1 < L - 1 ? i0 + kW - 1 : L - 1;
+        const int ip_min = j == 0 ? i0 : L - 1 - last;          // the smallest i' of this step's bases
+        if (ip_min >= DCR_BMET_CYC_BINS - 1) {
+            const uint32_t c0 = (uint32_t)bm_pop(act), c1 = (uint32_t)bm_pop(isn);
+            const uint32_t c2 = (uint32_t)bm_pop(act && cls == 1), c3 = (uint32_t)bm_pop(act && cls == 2);
+            const uint32_t ws = wave_sum(act ? sd : 0u), we = wave_sum(act ? se : 0u);
+            if (lane_id() == 0) {
+                const int b = DCR_BMET_CYC_BINS - 1;
+                atomicAdd(&Sh.cyc[j][0][b], c0);
+                if (c1) atomicAdd(&Sh.cyc[j][1][b], c1);
+                if (c2) atomicAdd(&Sh.cyc[j][2][b], c2);
+                if (c3) atomicAdd(&Sh.cyc[j][3][b], c3);
+                if (ws) atomicAdd(&Sh.sum[j][0][b], (unsigned long long)ws);
+                if (we) atomicAdd(&Sh.sum[j][1][b], (unsigned long long)we);
+            }
+        } else if (act) {
+            const int ip = j == 0 ? (int)i : L - 1 - (int)i;
+            const int b = ip < DCR_BMET_CYC_BINS - 1 ? ip : DCR_BMET_CYC_BINS - 1;
+            atomicAdd(&Sh.cyc[j][0][b], 1u);
+            if (isn) atomicAdd(&Sh.cyc[j][1][b], 1u);
+            if (cls == 1) atomicAdd(&Sh.cyc[j][2][b], 1u);
+            if (cls == 2) atomicAdd(&Sh.cyc[j][3][b], 1u);
+            if (sd) atomicAdd(&Sh.sum[j][0][b], (unsigned long long)sd);
+            if (se) atomicAdd(&Sh.sum[j][1][b], (unsigned long long)se);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBmThreads) void k_base_metrics(BaseMetricsArgs A) {
+    __shared__ BmShared S;
+    for (int i = threadIdx.x; i < (int)(sizeof(BmShared) / 4); i += kBmThreads) reinterpret_cast<uint32_t *>(&S)[i] = 0;
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * kBmThreads + threadIdx.x) / kW));
+    const int nw = (int)(gridDim.x * (kBmThreads / kW));
+    unsigned long long n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t k = 2 * (int64_t)A.f0 + wave; k < 2 * (int64_t)A.f1; k += nw) {
+        if (A.fam_fail[k >> 1] != 0) continue;
+        bm_record(A, S, k, n);
+    }
+    if (lane_id() == 0)
+        for (int t = 0; t < 8; ++t)
+            if (n[t]) atomicAdd(&S.n[t], n[t]);
+    __syncthreads();
+    // the workgroup's tables into the slot's: one 64-bit add per non-zero bin
+    unsigned long long *out = reinterpret_cast<unsigned long long *>(A.out);
+    for (int w = threadIdx.x; w < kBmWords; w += kBmThreads) {
+        unsigned long long v;
+        if (w < kBmPair) {
+            v = S.n[w];
+        } else if (w < kBmCyc) {
+            v = S.cnt[w - kBmPair];
+        } else {
+            const int t = w - kBmCyc, jj = t / (6 * DCR_BMET_CYC_BINS), what = t / DCR_BMET_CYC_BINS % 6;
+            const int b = t % DCR_BMET_CYC_BINS;
+            v = what < 4 ? (unsigned long long)S.cyc[jj][what][b] : S.sum[jj][what - 4][b];
+        }
+        if (v) atomicAdd(&out[w], v);
     }
 }
 

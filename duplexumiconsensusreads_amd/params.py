@@ -250,6 +250,64 @@ def metrics_json(words) -> str:
     return json.dumps(doc, sort_keys=True, separators=(",", ":")) + "\n"
 
 
+# ---- per-base duplex QC tables (include/dcr.h dcr_base_metrics; --base_metrics_output) ----
+BMET_DEPTH_BINS, BMET_ERR_BINS, BMET_QUAL_BINS, BMET_CYC_BINS = 64, 1002, 256, 512
+
+
+class DcrBaseMetrics(ctypes.Structure):
+    """Mirror of ``dcr_base_metrics`` (include/dcr.h): every field uint64."""
+    _fields_ = [("n", ctypes.c_uint64 * 8),
+                ("pair", ctypes.c_uint64 * 5 * 5 * 2),
+                ("depth", ctypes.c_uint64 * BMET_DEPTH_BINS * BMET_DEPTH_BINS),
+                ("err", ctypes.c_uint64 * BMET_ERR_BINS),
+                ("qual", ctypes.c_uint64 * BMET_QUAL_BINS * 3),
+                ("cyc", ctypes.c_uint64 * BMET_CYC_BINS * 6 * 2)]
+
+
+BMET_WORDS = ctypes.sizeof(DcrBaseMetrics) // 8       # 12,068
+BMET_N_NAMES = ("records", "bases", "both_strands", "a_only", "b_only", "neither", "disagree", "duplex_errors")
+BMET_CYC_NAMES = ("bases", "no_calls", "disagree", "single", "depth", "errors")
+
+
+def base_metrics_fields(words):
+    """The tables of a ``uint64[BMET_WORDS]`` block as a dict of array views,
+    shaped as the struct's fields."""
+    words = np.asarray(words).reshape(-1)
+    if len(words) != BMET_WORDS:
+        raise ValueError("not a dcr_base_metrics block")
+    out = {}
+    for name, ct in DcrBaseMetrics._fields_:
+        f = getattr(DcrBaseMetrics, name)
+        shape, t = [], ct
+        while hasattr(t, "_length_"):
+            shape.append(t._length_)
+            t = t._type_
+        out[name] = words[f.offset // 8:(f.offset + f.size) // 8].reshape(shape)
+    return out
+
+
+def base_metrics_json(words) -> str:
+    """The ``--base_metrics_output`` file of a counter block: sorted keys and
+    fixed separators, so the same counters always give the same bytes."""
+    import json
+    m = base_metrics_fields(words)
+    doc = {"version": 1,
+           "bins": {"depth_max": BMET_DEPTH_BINS - 1, "cycle_max": BMET_CYC_BINS - 1,
+                    "error_rate_other": BMET_ERR_BINS - 1, "error_rate_scale": 1000}}
+    for i, name in enumerate(BMET_N_NAMES):
+        doc[name] = int(m["n"][i])
+    doc["pair"] = {"codes": "ACGTN", "read1": [[int(v) for v in row] for row in m["pair"][0]],
+                   "read2": [[int(v) for v in row] for row in m["pair"][1]]}
+    doc["depth"] = [[int(h), int(lo), int(m["depth"][h, lo])] for h, lo in zip(*np.nonzero(m["depth"]))]
+    doc["err"] = [[int(b), int(m["err"][b])] for b in np.flatnonzero(m["err"])]
+    doc["qual"] = {k: _trimmed(m["qual"][i]) for i, k in enumerate(("agree", "disagree", "single"))}
+    doc["cycle"] = {}
+    for j, read in enumerate(("read1", "read2")):
+        n = len(_trimmed(m["cyc"][j, 0]))
+        doc["cycle"][read] = {k: [int(v) for v in m["cyc"][j, w, :n]] for w, k in enumerate(BMET_CYC_NAMES)}
+    return json.dumps(doc, sort_keys=True, separators=(",", ":")) + "\n"
+
+
 def _numbers(text, conv, most, what):
     parts = text.split(",")
     if not 1 <= len(parts) <= most:

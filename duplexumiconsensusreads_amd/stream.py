@@ -132,8 +132,9 @@ class _WriterOut:
 
         self.filt = None                 # pinned fam_filt, made when a filter is first set
         self.met = None                  # pinned dcr_metrics, made when metrics are first on
+        self.bmet = None                 # pinned dcr_base_metrics, made when base metrics are first on
 
-    def ensure(self, n_fam, bgzf_bytes, filt=False, met=False):
+    def ensure(self, n_fam, bgzf_bytes, filt=False, met=False, bmet=False):
         if n_fam > self.cap_f or self.small is None:
             self.cap_f = int(n_fam * 1.25) + 64
             self.small = Pinned(self.lib, 12 * self.cap_f + 64)
@@ -148,6 +149,10 @@ class _WriterOut:
             from .params import MET_WORDS
             self.met = Pinned(self.lib, 8 * MET_WORDS)
             self.metrics = self.met.array[:8 * MET_WORDS].view(np.uint64)
+        if bmet and self.bmet is None:
+            from .params import BMET_WORDS
+            self.bmet = Pinned(self.lib, 8 * BMET_WORDS)
+            self.base_metrics = self.bmet.array[:8 * BMET_WORDS].view(np.uint64)
         if bgzf_bytes > self.cap_b:
             self.cap_b = int(bgzf_bytes * 1.25) + (1 << 20)
             self.blocks = Pinned(self.lib, self.cap_b)
@@ -168,13 +173,16 @@ class WriterResult:
     ``fam_filt``: the per-family outcome words (low byte not 0: dropped, its
     records are not in the streams); None without one.  With ``metrics`` on,
     ``metrics``: the batch's dcr_metrics as uint64 words (the slot's pinned
-    block, overwritten when the slot is submitted again); None without."""
+    block, overwritten when the slot is submitted again); None without.  With
+    ``base_metrics`` on, ``base_metrics``: the batch's dcr_base_metrics in the
+    same way; None without."""
 
-    def __init__(self, stream, slot, out, n_fam, out_ss=None, filtered=False, metrics=False):
+    def __init__(self, stream, slot, out, n_fam, out_ss=None, filtered=False, metrics=False, base_metrics=False):
         self._stream, self._slot = stream, slot
         self.fam_fail = out.fam_fail[:n_fam]
         self.fam_filt = out.fam_filt[:n_fam] if filtered else None
         self.metrics = out.metrics if metrics else None
+        self.base_metrics = out.base_metrics if base_metrics else None
         self.ds_len = out.ds_len[:2 * n_fam]
         self.bgzf_bytes, self.record_bytes, self.blocks = (int(x) for x in out.totals[:3])
         self.bgzf = out.blocks.array[:self.bgzf_bytes]
@@ -225,7 +233,12 @@ class DeviceStream:
     ``base_tags`` (set per run too, --per_base_tags): the device writer writes
     the ten per-column tags of the duplex records, and sd / se of the
     single-strand ones, per base of SEQ (dcr_set_base_tags).  Device writer
-    only, for the per-base rules' reason; the host path ignores it."""
+    only, for the per-base rules' reason; the host path ignores it.
+
+    ``base_metrics`` (set per run too, --base_metrics_output): the device
+    writer counts the per-base duplex QC tables (dcr_set_base_metrics) and
+    ``result`` carries them as ``base_metrics``.  Device writer only, for the
+    same reason."""
 
     def __init__(self, ctx, n_slots=2, owns_ctx=False, device_writer=True, persistent=False):
         """``persistent``: ``close`` only drains the slots (the context and the
@@ -242,6 +255,7 @@ class DeviceStream:
         self.filter = None
         self.metrics = False
         self.base_tags = False
+        self.base_metrics = False
         self.wouts_ss = None
         self.lib = _lib.load()
         self.n_slots = n_slots
@@ -276,11 +290,15 @@ class DeviceStream:
             # compressed records are far smaller than the kernel outputs; grown on demand
             filtered = self.filter is not None
             counted = bool(self.metrics)
-            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered, counted)
+            based = bool(self.base_metrics)
+            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered, counted, based)
             # the context may serve other streams: its filter, metrics and tags are this stream's for this batch
             self.ctx.set_filter(self.filter)
             self.ctx.set_metrics(counted)
             self.ctx.set_base_tags(self.base_tags)
+            self.ctx.set_base_metrics(based)
+            if based:
+                _lib._check(self.lib.dcr_slot_base_metrics_out(self.ctx._ctx, slot, wo.bmet.ptr))
             if counted:
                 _lib._check(self.lib.dcr_slot_metrics_out(self.ctx._ctx, slot, wo.met.ptr))
             if filtered:
@@ -304,11 +322,11 @@ class DeviceStream:
                                                          ctypes.byref(ms), ctypes.byref(self._wres),
                                                          ctypes.byref(self._wres_ss)))
                 self.busy[slot] = True
-                return (slot, s.n_fam, True, filtered, counted)
+                return (slot, s.n_fam, True, filtered, counted, based)
             _lib._check(self.lib.dcr_submit_write(self.ctx._ctx, slot, ctypes.byref(self._b), ctypes.byref(m),
                                                   ctypes.byref(self._wres)))
             self.busy[slot] = True
-            return (slot, s.n_fam, False, filtered, counted)
+            return (slot, s.n_fam, False, filtered, counted, based)
         out = self.outs[slot]
         out.ensure(4 * s.n_fam, s.ss_cols, 2 * s.n_fam, s.ds_cols, s.n_reads,
                    SS_FIELDS_FULL if self.ss_output else SS_FIELDS)
@@ -343,7 +361,7 @@ class DeviceStream:
                     grown = True
             if not grown:
                 _lib._check(rc)
-            return WriterResult(self, slot, wo, n_fam, ws, handle[3], handle[4])
+            return WriterResult(self, slot, wo, n_fam, ws, handle[3], handle[4], handle[5])
         slot = handle
         _lib._check(self.lib.dcr_wait(self.ctx._ctx, slot))
         self.busy[slot] = False
@@ -371,7 +389,7 @@ class DeviceStream:
             if o.mem is not None:
                 o.mem.free()
         for w in self.wouts + (self.wouts_ss or []):
-            for m in (w.small, w.blocks, w.filt, w.met):
+            for m in (w.small, w.blocks, w.filt, w.met, w.bmet):
                 if m is not None:
                     m.free()
         if self.owns_ctx:

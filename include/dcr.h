@@ -339,7 +339,8 @@ typedef struct dcr_base_filter {
 /* NULL or active == 0: off (the default; nothing is launched, copied, zeroed
  * or allocated).  Holds for the batches submitted after the call.
  * dcr_slot_fetch what 6 (a batch submitted with a base filter set, or with
- * the per-base tags on, dcr_set_base_tags): one byte
+ * the per-base tags or the base metrics on, dcr_set_base_tags /
+ * dcr_set_base_metrics): one byte
  * per record, single-strand 4F then duplex 2F, 1 where the consensus kernels
  * stored the record's column map (it has insertion columns), 0 where the map
  * follows from pos and CIGAR (diagnostic; the tests read it). */
@@ -426,6 +427,71 @@ int dcr_set_metrics(dcr_ctx *ctx, int on);
  * stream and before the same event, so it is complete when
  * dcr_wait_write[_ss] returns.  NULL removes it. */
 int dcr_slot_metrics_out(dcr_ctx *ctx, int slot, dcr_metrics *pinned_dst);
+
+/* Per-base duplex QC tables (not a reference feature; the per-base half of the
+ * QC tables above: what a user would otherwise count over the per-base tags of
+ * the written file).  With base metrics on, dcr_submit_write[_ss] counts, over
+ * the families f of the batch with fam_fail[f] == 0 and before any filter masks
+ * or drops, every base of the duplex consensus as called.  Levels 1 and 2 are
+ * the per-base filters' above.  For duplex record r = 2f + j, called from
+ * a = 4f + 2j and b = a + 1, and base i in [0, len): (c, ia, ib, ca, cb) are
+ * exactly those of dcr_set_base_tags; every index is clamped to its record's
+ * region, and a column outside [0, n_de) counts as 0, as the tags do.
+ *   aD = ss.d[a][ca], aE = ss.e[a][ca], both 0 when strand a has no base in
+ *        the column (not clamped to 32767); bD, bE the same for strand b;
+ *        cE = ds.e[r][c]
+ *   x = code(ss.seq[a][ia]), y = code(ss.seq[b][ib]): A a 0, C c 1, G g 2,
+ *        T t 3, anything else 4
+ *   cls = 0 when both strands have a base and x == y (two 'N' agree), 1 when
+ *        both have a base and x != y, 2 otherwise
+ *   s = aD + bD, e = aE + bE
+ *   i' = i for j = 0 and len - 1 - i for j = 1: the cycle counted from the
+ *        read's sequencing 5' end (the orientation rule of dcr_metrics.col)
+ * Tables:
+ *   n[0] duplex records, [1] bases, [2] bases with both strands present, [3]
+ *        strand a only, [4] strand b only, [5] neither, [6] cls == 1, [7] cE > 0
+ *   pair[j][x][y]      bases with both strands present, in SEQ orientation;
+ *        split by j so that the reverse read can be folded by complementing
+ *   depth[min(max(aD, bD), 63)][min(min(aD, bD), 63)]   every base
+ *   err[bin]           every base; bin = (s > 0 && e <= s) ? (1000 * e) / s :
+ *        DCR_BMET_ERR_BINS - 1, integer division
+ *   qual[cls][ds.qual[r][i]]   every base, the quality as called (unmasked)
+ *   cyc[j][what][min(i', 511)]  what 0 bases, 1 ds.seq[r][i] == 'N', 2
+ *        cls == 1, 3 cls == 2, 4 sum of s, 5 sum of e
+ * Every table is an integer sum (the error bin too: no floating point), so
+ * totals over batches or devices are sums of the blocks in any order.
+ * Reading the per-base rules off the tables:
+ *   --filter_min_base_reads T,A,B masks the bases of the depth bins [hi][lo]
+ *        that fail hi + lo >= T, hi >= A, lo >= B (exact while T, A, B stay
+ *        below the clamp, 63);
+ *   --filter_require_strand_agreement masks n[7] bases;
+ *   --filter_max_base_error_rate X masks about the sum of err above bin
+ *        1000 * X (bin 1001 included): approximate, because the rule compares
+ *        in doubles and the bins are floors of integer quotients. */
+#define DCR_BMET_DEPTH_BINS 64
+#define DCR_BMET_ERR_BINS 1002
+#define DCR_BMET_QUAL_BINS 256
+#define DCR_BMET_CYC_BINS 512
+typedef struct dcr_base_metrics {
+    uint64_t n[8];
+    uint64_t pair[2][5][5];
+    uint64_t depth[DCR_BMET_DEPTH_BINS][DCR_BMET_DEPTH_BINS];
+    uint64_t err[DCR_BMET_ERR_BINS];
+    uint64_t qual[3][DCR_BMET_QUAL_BINS];
+    uint64_t cyc[2][6][DCR_BMET_CYC_BINS];
+} dcr_base_metrics;     /* 12,068 words, 96,544 bytes */
+/* on != 0: count (k_base_metrics, after the failure scan and k_metrics, before
+ * the filters); 0: off (the default; nothing is launched, copied, zeroed or
+ * allocated and no output byte changes).  The column maps are made as for a
+ * base filter or the per-base tags, and dcr_slot_fetch what 6 serves such a
+ * batch too.  Holds for the batches submitted after the call. */
+int dcr_set_base_metrics(dcr_ctx *ctx, int on);
+/* Where a slot's per-base counters go (pinned host memory, one
+ * dcr_base_metrics, written whole for every batch submitted on the slot while
+ * base metrics are on: the batch's own counts, not a running total): copied
+ * with fam_fail, on the same stream and before the same event, so it is
+ * complete when dcr_wait_write[_ss] returns.  NULL removes it. */
+int dcr_slot_base_metrics_out(dcr_ctx *ctx, int slot, dcr_base_metrics *pinned_dst);
 
 /* CPU restatement with the same contract (oracle/, test infrastructure):
    host pointers, single thread (or n_threads > 1) */
