@@ -1507,4 +1507,58 @@ int dcr_deflate_probe(dcr_ctx *c, const uint8_t *host, int64_t n, unsigned long 
     return DCR_OK;
 }
 
+// test entry (not in include/dcr.h; tests/test_gpu_deflate_blocks.py):
+// k_deflate alone over n host bytes, shaped so that a wrong byte shows.
+//   max_wg     0: the pipeline's grid, min(blocks, CUs x resident workgroups);
+//              else at most that many workgroups (1: one workgroup compresses
+//              every block in turn, on the LDS the block before left)
+//   use_claim  a zeroed block counter in DflArgs::claim, as the pipeline passes
+//   the device input is allocated to a multiple of 16 bytes (the staging loads
+//   16 at a time) and the bytes past n hold 0xff
+//   slots_out  (blocks + 1) x 65536 bytes: every slot and one guard slot behind
+//              the last are filled with `fill` before the launch and returned whole
+//   sizes_out  [blocks], -1 where the kernel wrote none
+int dcr_deflate_blocks(dcr_ctx *c, const uint8_t *host, int64_t n, int max_wg, int use_claim, int fill,
+                       uint8_t *slots_out, int64_t *sizes_out) {
+    if (!c || !host || n <= 0 || max_wg < 0 || !slots_out || !sizes_out) return fail(DCR_EARG, "bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t nb = (n + dfl::kMaxIn - 1) / dfl::kMaxIn;
+    const size_t n_in = ((size_t)n + 15) & ~(size_t)15, n_slots = (size_t)(nb + 1) * dfl::kSlot;
+    unsigned gd = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nb, (int64_t)c->n_cu * c->dfl_blocks));
+    if (max_wg) gd = std::min(gd, (unsigned)max_wg);
+    uint8_t *d_in = nullptr, *d_slots = nullptr;
+    int64_t *d_n = nullptr, *d_sizes = nullptr;
+    unsigned long long *d_claim = nullptr;
+    uint32_t *d_tok = nullptr;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMalloc(&d_in, n_in));
+        HIP_TRY(hipMalloc(&d_slots, n_slots));
+        HIP_TRY(hipMalloc(&d_n, 8));
+        HIP_TRY(hipMalloc(&d_sizes, 8 * (size_t)nb));
+        HIP_TRY(hipMalloc(&d_claim, 8));
+        HIP_TRY(hipMalloc(&d_tok, (size_t)gd * dfl::kTokWords * 4));
+        HIP_TRY(hipMemsetAsync(d_in, 0xff, n_in, c->stream));
+        HIP_TRY(hipMemsetAsync(d_slots, fill & 0xff, n_slots, c->stream));
+        HIP_TRY(hipMemsetAsync(d_sizes, 0xff, 8 * (size_t)nb, c->stream));
+        HIP_TRY(hipMemsetAsync(d_claim, 0, 8, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_in, host, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_n, &n, 8, hipMemcpyHostToDevice, c->stream));
+        dcrw::DflArgs D{d_in, d_n, d_slots, d_sizes, d_tok, nullptr, use_claim ? d_claim : nullptr};
+        hipLaunchKernelGGL(dcrw::k_deflate, dim3(gd), dim3(dfl::kT), sizeof(dfl::Shared), c->stream, D);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(sizes_out, d_sizes, 8 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(slots_out, d_slots, n_slots, hipMemcpyDeviceToHost));
+        return DCR_OK;
+    };
+    const int rc = run();
+    (void)hipFree(d_in);
+    (void)hipFree(d_slots);
+    (void)hipFree(d_n);
+    (void)hipFree(d_sizes);
+    (void)hipFree(d_claim);
+    (void)hipFree(d_tok);
+    return rc;
+}
+
 }  // extern "C"

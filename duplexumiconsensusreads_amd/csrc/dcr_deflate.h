@@ -1266,10 +1266,14 @@ DFL_HD inline void put_gzip_header(O &o, uint32_t bsize) {
 
 // ---- the phases (lane = thread index) -----------------------------------------
 // stored-or-compressed decision once the bits are known (any one lane)
+DFL_HD inline bool will_store(const Shared &s, uint32_t n, uint32_t end_bits) {
+    const uint32_t dbytes = (end_bits - 144 + s.lit_len[256] + 7) / 8;
+    return dbytes > kMaxDeflate || dbytes > n + 5;
+}
 DFL_HD inline void decide(Shared &s, uint32_t n, uint32_t end_bits) {
     s.body_bits = end_bits - 144 + s.lit_len[256];
     const uint32_t dbytes = (s.body_bits + 7) / 8;
-    s.stored = (dbytes > kMaxDeflate || dbytes > n + 5) ? 1u : 0u;
+    s.stored = will_store(s, n, end_bits) ? 1u : 0u;
     s.use_stage = (!s.stored && dbytes + 26 <= sizeof(s.stage)) ? 1u : 0u;
 }
 
@@ -1360,12 +1364,17 @@ DFL_HD inline void p4_bits(Shared &s, uint32_t n, int lane, const uint32_t *tok)
 // between P4 and P5, sequential form (the host emulation; the kernel runs
 // the same scan across the workgroup): bit offsets (deflate data begins at
 // byte 18 of the member), stored decision, CRC; zeroes the words two lanes
-// share, in both possible destinations (stage[] and the global slot)
+// share, in both possible destinations (stage[] and the global slot), unless
+// the block will be stored: its dynamic form is the longer one, and the words
+// of its last lanes would lie behind the stored member
 DFL_HD inline void p4_scan(Shared &s, uint32_t n, uint32_t *out) {
     uint32_t acc = 3 * 8 * 6 + s.hdr_bits;
+    for (int l = 0; l < kT; ++l) acc += s.lane_bits[l];
+    const bool keep = !will_store(s, n, acc);
+    acc = 3 * 8 * 6 + s.hdr_bits;
     for (int l = 0; l < kT; ++l) {
         s.lane_off[l] = acc;
-        if (l && (acc & 31)) {
+        if (keep && l && (acc & 31)) {
             out[acc >> 5] = 0;
             if ((acc >> 5) < sizeof(s.stage) / 4) s.stage[acc >> 5] = 0;
         }

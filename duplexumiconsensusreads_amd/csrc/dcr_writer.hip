@@ -1533,7 +1533,8 @@ __global__ __launch_bounds__(256) void k_famfail(FmtArgs A) {
 }
 
 // dfl::p4_scan across the workgroup: wave scans of the lanes' bit counts,
-// xor of their CRC registers; zeroes the words two lanes share
+// xor of their CRC registers; zeroes the words two lanes share (not of a
+// block that will be stored: every lane has the total after the barrier)
 __device__ __forceinline__ void p4_scan_wg(dfl::Shared &s, uint32_t n, int lane, uint32_t *slot) {
     const uint32_t b = s.lane_bits[lane];
     const uint32_t inc = wave_incl_scan(b);
@@ -1544,11 +1545,12 @@ __device__ __forceinline__ void p4_scan_wg(dfl::Shared &s, uint32_t n, int lane,
     if ((lane & (kW - 1)) == kW - 1) s.wave_sum[w] = inc;
     if ((lane & (kW - 1)) == 0) s.wave_crc[w] = cx;
     __syncthreads();
-    uint32_t base = 3 * 8 * 6 + s.hdr_bits;
+    uint32_t base = 3 * 8 * 6 + s.hdr_bits, end = base;
     for (int k = 0; k < w; ++k) base += s.wave_sum[k];
+    for (int k = 0; k < dfl::kT / kW; ++k) end += s.wave_sum[k];
     const uint32_t off = base + inc - b;
     s.lane_off[lane] = off;
-    if (lane && (off & 31)) {
+    if (lane && (off & 31) && !dfl::will_store(s, n, end)) {
         slot[off >> 5] = 0;
         if ((off >> 5) < sizeof(s.stage) / 4) s.stage[off >> 5] = 0;
     }

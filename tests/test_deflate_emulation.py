@@ -3,7 +3,9 @@ by lane on the host (dcr_deflate_emulate): every block must be one valid
 BGZF member (SAM spec v1.6 §4.1: BC extra field, BSIZE, CRC32, ISIZE) that
 zlib inflates back to the input, for compressible record text, random bytes
 (stored-block fallback), runs, tiny and full-size blocks.  The kernel runs
-the same phase code (tests/test_gpu_writer.py checks its stream)."""
+the same phase code (tests/test_gpu_writer.py checks its stream on record
+text; tests/test_gpu_deflate_blocks.py checks it block by block on the named
+inputs of tests/deflate_cases.py, the edges record text never reaches)."""
 import struct
 import zlib
 
