@@ -54,6 +54,8 @@ EXPORTS = {
     "dcr_slot_metrics_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "dcr_set_base_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "dcr_slot_base_metrics_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "dcr_set_mate_overlap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "dcr_slot_overlap_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     # include/dcr_inflate.h: BGZF inflate on the device
     "dcr_inflater_create": (ctypes.c_void_p, [ctypes.c_int]),
     "dcr_inflater_destroy": (None, [ctypes.c_void_p]),
@@ -132,6 +134,7 @@ class Context:
         self.metrics = False
         self.base_tags = False
         self.base_metrics = False
+        self.mate_overlap = 0
         if want_info:
             _check(lib.dcr_set_options(self._ctx, 1))
 
@@ -187,6 +190,16 @@ class Context:
             return
         _check(load().dcr_set_base_metrics(self._ctx, 1 if on else 0))
         self.base_metrics = bool(on)
+
+    def set_mate_overlap(self, mode):
+        """The device writer reconciles the overlapping mates (include/dcr.h
+        dcr_set_mate_overlap: 0 off, params.OVL_MASK, params.OVL_CONSENSUS)
+        for the batches it takes from now on."""
+        mode = int(mode or 0)
+        if mode == self.mate_overlap:
+            return
+        _check(load().dcr_set_mate_overlap(self._ctx, mode))
+        self.mate_overlap = mode
 
     @property
     def stream(self):

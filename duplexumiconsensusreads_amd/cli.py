@@ -46,6 +46,14 @@ read's length, instead of the reference's lists per alignment column
 (include/dcr.h ``dcr_set_base_tags``; device writer only).  Off by default;
 without it no output byte changes.
 
+``--mate_overlap mask|consensus`` (not a reference flag) reconciles the two
+duplex reads of a family where both cover the same reference position
+(include/dcr.h ``dcr_set_mate_overlap``): ``mask`` turns disagreeing bases into
+'N', ``consensus`` keeps the better base at the difference of the qualities and
+adds the qualities of agreeing bases (at most 93).  Only ``SEQ`` and ``QUAL`` of
+the duplex reads change; the step comes after the QC tables and before any
+``--filter_*``.  Off by default; without it no output byte changes.
+
 Batches are pipelined: a thread ingests batch k+1 while the device runs batch
 k and the main thread writes batch k-1.
 
@@ -152,6 +160,12 @@ def parse_args(argv):
     ap.add_argument("--per_base_tags", action="store_true",
                     help="write ad bd cd ae be ce as B:s arrays and ac bc aq bq as strings with one value per base "
                          "of SEQ (sd se of --single_strand_output likewise) instead of lists per alignment column")
+    # not a reference flag: the two duplex reads of a family where they overlap (include/dcr.h dcr_set_mate_overlap)
+    ap.add_argument("--mate_overlap", required=False, default=None, metavar="mask|consensus",
+                    type=params_mod.mate_overlap,
+                    help="where the two duplex reads of a family cover the same reference position: 'mask' turns "
+                         "disagreeing bases into 'N'; 'consensus' keeps the base of the higher quality at the "
+                         "difference of the two and gives agreeing bases the sum (at most 93)")
     return ap.parse_args(argv)
 
 
@@ -295,13 +309,15 @@ def gpu_inflate(device: int = 0):
 
 
 def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=False, base_tags=False,
-                base_metrics=False):
+                base_metrics=False, mate_overlap=0):
     """``ss_output``: this run also writes the single-strand records (a
     property of the run, set on the backend each time: the default backend
     is kept across runs).  ``flt``: this run's ConsensusFilter or None,
     set each time in the same way; so are ``metrics`` (--metrics_output),
-    ``base_tags`` (--per_base_tags) and ``base_metrics``
-    (--base_metrics_output)."""
+    ``base_tags`` (--per_base_tags), ``base_metrics``
+    (--base_metrics_output) and ``mate_overlap`` (--mate_overlap: 0 or a
+    params.OVL_* mode; the rule needs only the written record, so every
+    backend that carries the attribute supports it)."""
     if backend is None:
         be = default_backend(params, device)
     elif hasattr(backend, "submit"):
@@ -334,6 +350,10 @@ def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=Fa
         raise ValueError("this backend cannot count the per-base metrics")
     if hasattr(be, "base_metrics"):
         be.base_metrics = base_metrics
+    if hasattr(be, "mate_overlap"):
+        be.mate_overlap = mate_overlap or 0
+    elif mate_overlap:
+        raise ValueError("this backend cannot reconcile the overlapping mates")
     return be
 
 
@@ -406,6 +426,10 @@ class _Driver:
         # families dropped by the filter, per reason, and bases masked in the written ones (the summary's counters)
         self.filter_counts = {} if self.filter is None else dict(
             {"filter_dropped": 0, "filter_masked": 0}, **{"filter_" + name: 0 for _, name in params_mod.FILT_REASONS})
+        # --mate_overlap: the mode and the counters of the families written (the summary's)
+        self.overlap = args.mate_overlap or 0
+        self.overlap_counts = {} if not self.overlap else {"overlap_compared": 0, "overlap_disagree": 0,
+                                                           "overlap_changed": 0}
         # per-stage busy seconds and totals (bench.py --e2e reports them)
         self.trace = None          # optional [(stage, t0, t1)] (bench.py)
         self.ends_at_eof = True    # False for a sharded range that stops before the end
@@ -413,6 +437,7 @@ class _Driver:
                       "submit_s": 0.0, "wait_s": 0.0, "write_s": 0.0, "idle_s": 0.0}
         if self.filter is not None:
             self.stats.update(filter_dropped_families=0, filter_masked_bases=0)
+        self.stats.update(self.overlap_counts)
         # --metrics_output: the batches' counters summed at once (a device slot's block is overwritten on reuse)
         self.metrics_total = np.zeros(params_mod.MET_WORDS, np.uint64) if args.metrics_output is not None else None
         self.base_metrics_total = (np.zeros(params_mod.BMET_WORDS, np.uint64)
@@ -557,6 +582,7 @@ class _Driver:
                     self.sscs.write(res.ss_record_bytes_of(fail_f))
             lens = res.ds_len[:2 * fail_f]
             filt = res.fam_filt[:fail_f] if self.filter is not None else None
+            ovl = res.fam_ovl[:3 * fail_f] if self.overlap else None
             if self.metrics_total is not None:
                 self.metrics_total += res.metrics
             if self.base_metrics_total is not None:
@@ -568,6 +594,8 @@ class _Driver:
             if self.metrics_total is not None:
                 # before the filter, which masks the duplex arrays in place
                 self.metrics_total += native_io.metrics(hb, ss, ds, fail_f)
+            # after the tables (the consensus as called), before the filter (which sees what this leaves)
+            ovl = native_io.apply_overlap(hb, ss, ds, self.overlap, fail_f) if self.overlap else None
             filt = native_io.apply_filter(hb, ss, ds, self.filter, fail_f) if self.filter is not None else None
             self.cons.write_consensus(hb, ss, ds, fail_f, filt)
             if self.sscs is not None:
@@ -590,6 +618,12 @@ class _Driver:
             for bit, name in params_mod.FILT_REASONS:
                 fc["filter_" + name] += int(((why & bit) != 0).sum())
             st["filter_dropped_families"], st["filter_masked_bases"] = fc["filter_dropped"], fc["filter_masked"]
+        if ovl is not None:
+            # written families only: the families before a failure count, the dropped ones do not
+            per = ovl.reshape(-1, 3) if filt is None else ovl.reshape(-1, 3)[(filt & 0xff) == 0]
+            for i, key in enumerate(("overlap_compared", "overlap_disagree", "overlap_changed")):
+                self.overlap_counts[key] += int(per[:, i].sum())
+            st.update(self.overlap_counts)
         st["wait_s"] += t1 - t0
         if fail_f < F:
             t = int(np.nonzero(hb.a["tab_proc"][:hb.s.n_tab] == fail_f)[0][0])
@@ -758,7 +792,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
     bmet_path, bmet_total = args.base_metrics_output, None
     try:
         be = _as_backend(backend, params, args.device, ss_path is not None, ConsensusFilter.from_args(args),
-                         met_path is not None, args.per_base_tags, bmet_path is not None)
+                         met_path is not None, args.per_base_tags, bmet_path is not None, args.mate_overlap)
         cons, excl, unproc, *rest = _open_writers(
             [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
              "%s_filteredfamilies.bam" % consensus_filename[:-4]] + ([ss_path] if ss_path else []), ing.header, args,
@@ -786,6 +820,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
         if stats is not None:
             stats.update(c)
         c.update(drv.filter_counts)
+        c.update(drv.overlap_counts)
         if args.verbose:
             print("\n Input file has been completely read \n")
         _print_summary(c)
@@ -858,6 +893,12 @@ def _print_summary(c):
         print("\n Families removed per rule: " + ", ".join("%s %d" % (name, c["filter_" + name])
                                                             for _, name in params_mod.FILT_REASONS))
         print("\n A total of %d bases were masked in the consensus reads that were written." % c["filter_masked"])
+    if "overlap_compared" in c:
+        # only with --mate_overlap: of the consensus reads that were written
+        print("\n A total of %d reference positions covered by both reads of a pair were compared."
+              % c["overlap_compared"])
+        print("\n A total of %d of them held two different bases." % c["overlap_disagree"])
+        print("\n A total of %d bases were changed where the reads of a pair overlap." % c["overlap_changed"])
 
 
 # -- sharded mode: one process per GPU over ranges of whole families ---------------
@@ -962,7 +1003,8 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
                            params.min_base_quality, args.threads, rng_range[0], rng_range[1],
                            ss_meta=len(parts) > 3)
     be = _as_backend(backend, params, device, len(parts) > 3, ConsensusFilter.from_args(args),
-                     args.metrics_output is not None, args.per_base_tags, args.base_metrics_output is not None)
+                     args.metrics_output is not None, args.per_base_tags, args.base_metrics_output is not None,
+                     args.mate_overlap)
     cons, excl, unproc, *rest = _open_writers(parts, header, args, ing)
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng_state)
@@ -981,7 +1023,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
         res["status"], res["exc_args"] = "error", (repr(e),)
     finally:
         res["calls"] = ing.sample_calls()
-        res["counters"] = dict(ing.counters(), **drv.filter_counts)
+        res["counters"] = dict(ing.counters(), **drv.filter_counts, **drv.overlap_counts)
         res["metrics"] = drv.metrics_total
         res["base_metrics"] = drv.base_metrics_total
         res["stats"] = dict(drv.stats)

@@ -225,6 +225,7 @@ struct WriterBufs {
     // k_consensus_general_map stores for them
     dcr::BaseMap bmap;
     dcr_base_metrics *base_metrics;   // k_base_metrics' accumulator; null unless base metrics are on (dcr_set_base_metrics)
+    int32_t *fam_ovl;       // k_mate_overlap's counters [3F]; null unless a mode is set (dcr_set_mate_overlap)
 };
 
 // The second stream of dcr_submit_write_ss: the single-strand records'
@@ -269,10 +270,10 @@ void plan_writer_ss(int64_t F, Plan &p, WriterSsBufs &ws) {
 // k_base_filter's counts and with maps (the batch, when a base filter or the
 // per-base tags or the base metrics are on) the column maps, after every
 // other region (none without them); with bmet, k_base_metrics' accumulator
-// after those
+// after those; with ovl (dcr_set_mate_overlap) k_mate_overlap's counters last
 void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w,
                  WriterSsBufs *ws = nullptr, bool filt = false, bool met = false, const dcr_batch *maps = nullptr,
-                 bool bfilt = false, bool bmet = false) {
+                 bool bfilt = false, bool bmet = false, bool ovl = false) {
     w.names = p.take<char>((size_t)n_names + 1);
     w.fam_code = p.take<int64_t>((size_t)F);
     w.fam_rx = p.take<int64_t>(2 * (size_t)F);
@@ -302,6 +303,7 @@ void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd
         w.bmap.ds_aln = p.take<uint32_t>((size_t)maps->ds_cols);
     }
     w.base_metrics = bmet ? p.take<dcr_base_metrics>(1) : nullptr;
+    w.fam_ovl = ovl ? p.take<int32_t>(3 * (size_t)F) : nullptr;
 }
 }  // namespace
 
@@ -348,6 +350,7 @@ struct dcr_ctx {
         int32_t *h_fam_filt = nullptr;   // the caller's pinned fam_filt (dcr_slot_filter_out), or null
         dcr_metrics *h_metrics = nullptr;   // the caller's pinned counters (dcr_slot_metrics_out), or null
         dcr_base_metrics *h_base_metrics = nullptr;   // the same for dcr_slot_base_metrics_out
+        int32_t *h_fam_ovl = nullptr;    // the caller's pinned fam_ovl (dcr_slot_overlap_out), or null
         bool busy = false;
     } slots[DCR_MAX_SLOTS];
     dcr::Workspace w{};
@@ -362,6 +365,7 @@ struct dcr_ctx {
     dcr_base_filter base_filter{};   // dcr_set_base_filter; active == 0: off
     bool base_tags = false;          // dcr_set_base_tags
     bool base_metrics = false;       // dcr_set_base_metrics
+    int mate_overlap = 0;            // dcr_set_mate_overlap: 0 off, DCR_OVL_MASK, DCR_OVL_CONSENSUS
     // the column maps of the batch being submitted (submit_write sets them around its
     // dcr_run_batch when a base filter, the per-base tags or the base metrics are on); all null otherwise
     dcr::BaseMap bmap{};
@@ -1077,11 +1081,16 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         return fail(DCR_EARG, "metrics are on but the slot has no destination (dcr_slot_metrics_out)");
     if (bmet && !S.h_base_metrics)
         return fail(DCR_EARG, "base metrics are on but the slot has no destination (dcr_slot_base_metrics_out)");
+    const bool ovl = c->mate_overlap != 0;
+    if (ovl && F && !S.h_fam_ovl)
+        return fail(DCR_EARG, "a mate overlap mode is set but the slot has no fam_ovl destination (dcr_slot_overlap_out)");
     Plan wsz;
-    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt, bmet);
+    plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt, bmet,
+                ovl);
     if (wsz.off > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wsz.off + wsz.off / 8));
     Plan wp{(char *)S.wbuf.p};
-    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt, bmet);
+    plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt, bmet,
+                ovl);
     // H2D: inputs and writer metadata on the copy stream
     HIP_TRY(upload_inputs(h, db, c->s_h2d));
     if (m->n_names) HIP_TRY(hipMemcpyAsync(wb.names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
@@ -1167,6 +1176,13 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
                 hipLaunchKernelGGL(dcrw::k_base_metrics, dim3(gb), dim3(dcrw::kBmThreads), 0, c->stream, Ba);
                 f0 = f1;
             }
+        }
+        if (ovl) {
+            // one wave per family, after the QC tables (they describe the consensus as called) and
+            // before the filters, which see the two mates as this step leaves them
+            dcrw::MateOverlapArgs Oa{dout[1], db.ds_col_off, wb.fam_fail, wb.fam_ovl, (int32_t)F, c->mate_overlap};
+            const unsigned go = (unsigned)std::max<int64_t>(1, std::min<int64_t>((F + 3) / 4, (int64_t)c->n_cu * 8));
+            hipLaunchKernelGGL(dcrw::k_mate_overlap, dim3(go), dim3(256), 0, c->stream, Oa);
         }
         if (filt) {
             // one wave per family, before anything reads the duplex seq / qual
@@ -1268,6 +1284,7 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
         HIP_TRY(hipMemcpyAsync(res->fam_fail, wb.fam_fail, 4 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
         HIP_TRY(hipMemcpyAsync(res->ds_len, wb.ds_len, 8 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
         if (filt) HIP_TRY(hipMemcpyAsync(S.h_fam_filt, wb.fam_filt, 4 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
+        if (ovl) HIP_TRY(hipMemcpyAsync(S.h_fam_ovl, wb.fam_ovl, 12 * (size_t)F, hipMemcpyDeviceToHost, c->s_d2h));
     }
     if (met) HIP_TRY(hipMemcpyAsync(S.h_metrics, wb.metrics, sizeof(dcr_metrics), hipMemcpyDeviceToHost, c->s_d2h));
     if (bmet)
@@ -1332,6 +1349,21 @@ int dcr_slot_filter_out(dcr_ctx *c, int slot, int32_t *fam_filt) {
     if (!c || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
     if (c->slots[slot].busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
     c->slots[slot].h_fam_filt = fam_filt;
+    return DCR_OK;
+}
+
+int dcr_set_mate_overlap(dcr_ctx *c, int mode) {
+    if (!c) return fail(DCR_EARG, "NULL context");
+    if (mode != 0 && mode != DCR_OVL_MASK && mode != DCR_OVL_CONSENSUS)
+        return fail(DCR_EARG, "mate overlap mode must be 0, DCR_OVL_MASK or DCR_OVL_CONSENSUS");
+    c->mate_overlap = mode;
+    return DCR_OK;
+}
+
+int dcr_slot_overlap_out(dcr_ctx *c, int slot, int32_t *fam_ovl) {
+    if (!c || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
+    if (c->slots[slot].busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
+    c->slots[slot].h_fam_ovl = fam_ovl;
     return DCR_OK;
 }
 

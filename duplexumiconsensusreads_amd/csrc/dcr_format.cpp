@@ -644,6 +644,94 @@ int dcr_fmt_filter(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fm
     return DCR_IO_OK;
 }
 
+// the overlapping mates of include/dcr.h (dcr_set_mate_overlap), as dcr_writer.hip's k_mate_overlap
+// rewrites them: the two CIGARs walked run by run, the run that ends first advanced
+struct MoRec {
+    const uint32_t *cig;
+    uint8_t *seq, *qual;
+    int64_t len, ncig, pos;
+};
+struct MoCur {
+    int64_t k, rp, bi;      // next operation, its reference position and base index
+    int64_t r0, b0, n;      // the M run found last (n == 0: none left)
+};
+static void mo_next(const MoRec &R, MoCur &c) {
+    c.n = 0;
+    while (c.k < R.ncig && c.bi < R.len) {
+        const uint32_t v = R.cig[c.k++];
+        const int64_t n = v >> 4;
+        const uint32_t op = v & 15u;
+        if (op == 0u || op == 7u || op == 8u) {
+            c.r0 = c.rp;
+            c.b0 = c.bi;
+            c.n = std::min(n, R.len - c.bi);
+            c.rp += n;
+            c.bi += n;
+            if (c.n > 0) return;
+        } else if (op == 1u || op == 4u) {
+            c.bi += n;
+        } else if (op == 2u || op == 3u) {
+            c.rp += n;
+        }
+    }
+}
+
+int dcr_fmt_mate_overlap(const dcr_host_batch *hb, const dcr_fmt_out *ds, int mode, int32_t n_fam, int32_t *fam_ovl) {
+    if (!hb || !ds || !fam_ovl || n_fam < 0 || n_fam > hb->n_fam || (mode != DCR_OVL_MASK && mode != DCR_OVL_CONSENSUS))
+        return fail(DCR_IO_EARG, "bad arguments");
+    auto clampi = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : v > hi ? hi : v; };
+    for (int32_t f = 0; f < n_fam; ++f) {
+        MoRec R[2];
+        for (int j = 0; j < 2; ++j) {
+            const int32_t k = 2 * f + j;
+            const int64_t ro = hb->ds_col_off[k], room = hb->ds_col_off[k + 1] - ro;
+            R[j] = MoRec{ds->cigar + ro, const_cast<uint8_t *>(ds->seq) + ro, const_cast<uint8_t *>(ds->qual) + ro,
+                         clampi(ds->len[k], room), clampi(ds->n_cig[k], room), ds->pos[k]};
+        }
+        uint32_t cmp = 0, dis = 0, chg = 0;
+        MoCur c0{0, R[0].pos, 0, 0, 0, 0}, c1{0, R[1].pos, 0, 0, 0, 0};
+        mo_next(R[0], c0);
+        mo_next(R[1], c1);
+        while (c0.n > 0 && c1.n > 0) {
+            const int64_t e0 = c0.r0 + c0.n, e1 = c1.r0 + c1.n;
+            const int64_t lo = std::max(c0.r0, c1.r0), hi = std::min(e0, e1);
+            for (int64_t p = lo; p < hi; ++p) {
+                uint8_t &x = R[0].seq[c0.b0 + (p - c0.r0)], &qx = R[0].qual[c0.b0 + (p - c0.r0)];
+                uint8_t &y = R[1].seq[c1.b0 + (p - c1.r0)], &qy = R[1].qual[c1.b0 + (p - c1.r0)];
+                if (x == 'N' || y == 'N') continue;
+                ++cmp;
+                uint8_t nx = x, nqx = qx, ny = y, nqy = qy;
+                if (x == y) {
+                    if (mode == DCR_OVL_CONSENSUS) nqx = nqy = (uint8_t)std::min(qx + qy, 93);
+                } else {
+                    ++dis;
+                    if (mode == DCR_OVL_CONSENSUS && qx != qy) {
+                        nx = ny = qx > qy ? x : y;
+                        nqx = nqy = (uint8_t)(qx > qy ? qx - qy : qy - qx);
+                    } else {
+                        nx = ny = 'N';
+                        nqx = std::min<uint8_t>(qx, 2);
+                        nqy = std::min<uint8_t>(qy, 2);
+                    }
+                }
+                chg += (nx != x || nqx != qx) + (ny != y || nqy != qy);
+                x = nx;
+                qx = nqx;
+                y = ny;
+                qy = nqy;
+            }
+            if (e0 <= e1)
+                mo_next(R[0], c0);
+            else
+                mo_next(R[1], c1);
+        }
+        fam_ovl[3 * f] = (int32_t)cmp;
+        fam_ovl[3 * f + 1] = (int32_t)dis;
+        fam_ovl[3 * f + 2] = (int32_t)chg;
+    }
+    return DCR_IO_OK;
+}
+
 // the tables of include/dcr.h (dcr_metrics), as dcr_writer.hip's k_metrics counts them
 static int met_err_bin(double E) {
     // one double multiply (built with -ffp-contract=off); NaN fails both compares

@@ -115,6 +115,16 @@ struct BaseMetricsArgs {
 };
 constexpr int kBmThreads = 1024;    // k_base_metrics' workgroup: 16 waves on one set of LDS tables
 
+// the overlapping mates (k_mate_overlap, dcr_set_mate_overlap)
+struct MateOverlapArgs {
+    dcr_out ds;                     // device kernel outputs; ds.seq / ds.qual are rewritten in place
+    const int64_t *ds_col_off;      // [2F+1]
+    const int32_t *fam_fail;        // [F] from k_famfail
+    int32_t *fam_ovl;               // [3F] compared, disagree, changed
+    int32_t n_fam;
+    int32_t mode;                   // DCR_OVL_MASK or DCR_OVL_CONSENSUS
+};
+
 struct DflArgs {
     const uint8_t *stream;
     const int64_t *stream_bytes;    // device scalar (rec_off[2F])
@@ -147,6 +157,7 @@ __global__ void k_fmt_write_tags(FmtTagArgs T);
 __global__ void k_fmt_size_ss_tags(FmtSsArgs A);
 __global__ void k_fmt_write_ss_tags(FmtSsTagArgs T);
 __global__ void k_base_metrics(BaseMetricsArgs A);
+__global__ void k_mate_overlap(MateOverlapArgs A);
 __global__ void k_deflate(DflArgs D);
 __global__ void k_compact(CompactArgs C);
 

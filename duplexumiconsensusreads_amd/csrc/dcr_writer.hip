@@ -1894,4 +1894,146 @@ hipError_t scan_excl_i64(const int64_t *in, int64_t *out, int n, int64_t *tmp, h
     return hipGetLastError();
 }
 
+// ---- the overlapping mates (dcr_set_mate_overlap; include/dcr.h states the
+// map and the rules).  One wave per family in 256-lane blocks, as k_filter;
+// runs after the QC tables and before the filters.  The map is the written
+// record's (pos, CIGAR, len), not the stored column maps.
+//
+// A lane owns pairs, not bases: it takes reference positions of an
+// intersection of an M run of mate 1 with an M run of mate 2, finds the two
+// base indices by subtraction, loads both bases and qualities as bytes and
+// stores what changed as bytes.  A base has one reference position and a
+// position one base per mate, so a pair (i0, i1) belongs to exactly one lane
+// and no lane reads a byte another lane writes: no barrier, no second pass,
+// no LDS.  (The two records' windows are misaligned against each other by
+// (pos1 - pos0) mod 4, so dword accesses would need a funnel shift on one
+// side and a read-modify-write on words two lanes share; a family's overlap
+// is a few hundred bytes.)
+//
+// When both CIGARs are one M run the intersection is lane arithmetic.
+// Otherwise the wave walks the two CIGARs run by run (every lane the same
+// walk: the wave index comes from readfirstlane, so its branches are
+// wave-uniform), always advancing the run that ends first, and the lanes
+// stride each intersection: the work follows the number of runs, never the
+// length of a D or N run.  len, n_cig and, through them, every base index are
+// clamped to the record's region (as bf_rec does); positions are 64-bit.
+struct MoRec {
+    const uint32_t *cig;
+    uint8_t *seq, *qual;
+    int64_t len, ncig, pos;
+};
+// a place in a CIGAR (next operation k, its reference position rp and base
+// index bi) and the M run found last: n bases from base b0 at position r0
+struct MoCur {
+    int64_t k, rp, bi;
+    int64_t r0, b0, n;      // n == 0: no run left
+};
+
+__device__ __forceinline__ void mo_rec(const dcr_out &o, const int64_t *col_off, int64_t r, MoRec &R) {
+    const int64_t ro = col_off[r], room = col_off[r + 1] - ro;
+    R.cig = o.cigar + ro;
+    R.seq = o.seq + ro;
+    R.qual = o.qual + ro;
+    R.len = bf_clamp(o.len[r], room);
+    R.ncig = bf_clamp(o.n_cig[r], room);
+    R.pos = o.pos[r];
+}
+
+// the next M / = / X run that still holds a base of the map
+__device__ __forceinline__ void mo_next(const MoRec &R, MoCur &c) {
+    c.n = 0;
+    while (c.k < R.ncig && c.bi < R.len) {
+        const uint32_t v = R.cig[c.k++];
+        const int64_t n = v >> 4;
+        const uint32_t op = v & 15u;
+        if (op == 0u || op == 7u || op == 8u) {
+            const int64_t left = R.len - c.bi;
+            c.r0 = c.rp;
+            c.b0 = c.bi;
+            c.n = n < left ? n : left;
+            c.rp += n;
+            c.bi += n;
+            if (c.n > 0) return;
+        } else if (op == 1u || op == 4u) {
+            c.bi += n;
+        } else if (op == 2u || op == 3u) {
+            c.rp += n;
+        }                   // H, P and the unused codes: neither
+    }
+}
+
+// n positions from base i0 of mate 1 and base i1 of mate 2, strided by the lanes
+__device__ __forceinline__ void mo_segment(const MoRec &R0, const MoRec &R1, int64_t i0, int64_t i1, int64_t n, int mode,
+                                           uint32_t &cmp, uint32_t &dis, uint32_t &chg) {
+    for (int64_t t = lane_id(); t < n; t += kW) {
+        const int64_t a = i0 + t, b = i1 + t;
+        const uint32_t x = R0.seq[a], qx = R0.qual[a], y = R1.seq[b], qy = R1.qual[b];
+        if (x == 'N' || y == 'N') continue;
+        ++cmp;
+        uint32_t nx = x, nqx = qx, ny = y, nqy = qy;
+        if (x == y) {
+            if (mode == DCR_OVL_CONSENSUS) nqx = nqy = qx + qy < 93u ? qx + qy : 93u;
+        } else {
+            ++dis;
+            if (mode == DCR_OVL_CONSENSUS && qx != qy) {
+                nx = ny = qx > qy ? x : y;
+                nqx = nqy = qx > qy ? qx - qy : qy - qx;
+            } else {
+                nx = ny = 'N';
+                nqx = qx < 2u ? qx : 2u;
+                nqy = qy < 2u ? qy : 2u;
+            }
+        }
+        if (nx != x) R0.seq[a] = (uint8_t)nx;
+        if (nqx != qx) R0.qual[a] = (uint8_t)nqx;
+        if (ny != y) R1.seq[b] = (uint8_t)ny;
+        if (nqy != qy) R1.qual[b] = (uint8_t)nqy;
+        chg += (nx != x || nqx != qx ? 1u : 0u) + (ny != y || nqy != qy ? 1u : 0u);
+    }
+}
+
+__device__ __forceinline__ bool mo_is_m(uint32_t v) { return (v & 15u) == 0u || (v & 15u) == 7u || (v & 15u) == 8u; }
+
+__global__ __launch_bounds__(256) void k_mate_overlap(MateOverlapArgs A) {
+    const int64_t wpb = blockDim.x / kW;
+    const int64_t wave = (int64_t)blockIdx.x * wpb + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kW));
+    const int64_t nw = (int64_t)gridDim.x * wpb;
+    for (int64_t f = wave; f < A.n_fam; f += nw) {
+        uint32_t cmp = 0, dis = 0, chg = 0;
+        if (A.fam_fail[f] == 0) {
+            MoRec R0, R1;
+            mo_rec(A.ds, A.ds_col_off, 2 * f, R0);
+            mo_rec(A.ds, A.ds_col_off, 2 * f + 1, R1);
+            if (R0.ncig == 1 && R1.ncig == 1 && mo_is_m(R0.cig[0]) && mo_is_m(R1.cig[0])) {
+                const int64_t m0 = R0.cig[0] >> 4, m1 = R1.cig[0] >> 4;
+                const int64_t n0 = m0 < R0.len ? m0 : R0.len, n1 = m1 < R1.len ? m1 : R1.len;
+                const int64_t lo = R0.pos > R1.pos ? R0.pos : R1.pos;
+                const int64_t hi = R0.pos + n0 < R1.pos + n1 ? R0.pos + n0 : R1.pos + n1;
+                mo_segment(R0, R1, lo - R0.pos, lo - R1.pos, hi - lo, A.mode, cmp, dis, chg);
+            } else {
+                MoCur c0{0, R0.pos, 0, 0, 0, 0}, c1{0, R1.pos, 0, 0, 0, 0};
+                mo_next(R0, c0);
+                mo_next(R1, c1);
+                while (c0.n > 0 && c1.n > 0) {
+                    const int64_t e0 = c0.r0 + c0.n, e1 = c1.r0 + c1.n;
+                    const int64_t lo = c0.r0 > c1.r0 ? c0.r0 : c1.r0, hi = e0 < e1 ? e0 : e1;
+                    mo_segment(R0, R1, c0.b0 + (lo - c0.r0), c1.b0 + (lo - c1.r0), hi - lo, A.mode, cmp, dis, chg);
+                    if (e0 <= e1)
+                        mo_next(R0, c0);
+                    else
+                        mo_next(R1, c1);
+                }
+            }
+            cmp = wave_sum(cmp);
+            dis = wave_sum(dis);
+            chg = wave_sum(chg);
+        }
+        if (lane_id() == 0) {
+            A.fam_ovl[3 * f] = (int32_t)cmp;
+            A.fam_ovl[3 * f + 1] = (int32_t)dis;
+            A.fam_ovl[3 * f + 2] = (int32_t)chg;
+        }
+    }
+}
+
 }  // namespace dcrw

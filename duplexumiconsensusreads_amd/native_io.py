@@ -105,6 +105,7 @@ def load():
             "dcr_fmt_write_ss": (_i32, [_vp, _vp, _vp, _i32]),
             "dcr_fmt_filter": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
             "dcr_fmt_metrics": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
+            "dcr_fmt_mate_overlap": (_i32, [_vp, _vp, _i32, _i32, _vp]),
             "dcr_fmt_write_filt": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
             "dcr_fmt_write_ss_filt": (_i32, [_vp, _vp, _vp, _i32, _vp]),
             "dcr_synth_write": (_i32, [_vp, _vp, _i32]),
@@ -445,6 +446,19 @@ def apply_filter(hb: HostBatch, ss: FmtOut, ds: FmtOut, flt, n_fam: int) -> np.n
                              out.ctypes.data) != 0:
         raise _err("consensus filter")
     return out[:n_fam]
+
+
+def apply_overlap(hb: HostBatch, ss: FmtOut, ds: FmtOut, mode: int, n_fam: int) -> np.ndarray:
+    """dcr_fmt_mate_overlap: the overlapping mates (include/dcr.h
+    dcr_set_mate_overlap; ``mode`` params.OVL_MASK or OVL_CONSENSUS) of
+    processed families [0, n_fam), none of which fails.  Rewrites the duplex
+    seq / qual arrays in place (``ss`` is not touched); returns fam_ovl[3 *
+    n_fam]: compared, disagree, changed per family.  To be called after
+    ``metrics`` and before ``apply_filter``."""
+    out = np.zeros(max(3 * n_fam, 1), np.int32)
+    if load().dcr_fmt_mate_overlap(ctypes.byref(hb.s), ctypes.byref(ds), int(mode), n_fam, out.ctypes.data) != 0:
+        raise _err("mate overlap")
+    return out[:3 * n_fam]
 
 
 def metrics(hb: HostBatch, ss: FmtOut, ds: FmtOut, n_fam: int, fam_fail=None) -> np.ndarray:

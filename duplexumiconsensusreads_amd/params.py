@@ -366,6 +366,18 @@ def filter_min_mean_base_quality(text):
     return v
 
 
+# ---- overlapping mates (include/dcr.h dcr_set_mate_overlap; --mate_overlap) ------
+OVL_OFF, OVL_MASK, OVL_CONSENSUS = 0, 1, 2
+OVL_MODES = {"mask": OVL_MASK, "consensus": OVL_CONSENSUS}
+
+
+def mate_overlap(text):
+    """``mask`` or ``consensus``: the DCR_OVL_* mode."""
+    if text not in OVL_MODES:
+        raise ValueError("--mate_overlap must be 'mask' or 'consensus'")
+    return OVL_MODES[text]
+
+
 @dataclasses.dataclass(frozen=True)
 class ConsensusFilter:
     """The ``--filter_*`` options, parsed; None = that rule is off."""

@@ -133,8 +133,9 @@ class _WriterOut:
         self.filt = None                 # pinned fam_filt, made when a filter is first set
         self.met = None                  # pinned dcr_metrics, made when metrics are first on
         self.bmet = None                 # pinned dcr_base_metrics, made when base metrics are first on
+        self.ovl = None                  # pinned fam_ovl, made when --mate_overlap is first set
 
-    def ensure(self, n_fam, bgzf_bytes, filt=False, met=False, bmet=False):
+    def ensure(self, n_fam, bgzf_bytes, filt=False, met=False, bmet=False, ovl=False):
         if n_fam > self.cap_f or self.small is None:
             self.cap_f = int(n_fam * 1.25) + 64
             self.small = Pinned(self.lib, 12 * self.cap_f + 64)
@@ -145,6 +146,11 @@ class _WriterOut:
         if filt and (self.filt is None or self.filt.nbytes < 4 * self.cap_f):
             self.filt = Pinned(self.lib, 4 * self.cap_f)
             self.fam_filt = self.filt.array.view(np.int32)
+        if ovl and (self.ovl is None or self.ovl.nbytes < 12 * self.cap_f):
+            if self.ovl is not None:
+                self.ovl.free()
+            self.ovl = Pinned(self.lib, 12 * self.cap_f)
+            self.fam_ovl = self.ovl.array.view(np.int32)
         if met and self.met is None:
             from .params import MET_WORDS
             self.met = Pinned(self.lib, 8 * MET_WORDS)
@@ -175,14 +181,17 @@ class WriterResult:
     ``metrics``: the batch's dcr_metrics as uint64 words (the slot's pinned
     block, overwritten when the slot is submitted again); None without.  With
     ``base_metrics`` on, ``base_metrics``: the batch's dcr_base_metrics in the
-    same way; None without."""
+    same way; None without.  With ``mate_overlap`` set, ``fam_ovl``: compared,
+    disagree, changed per family (int32 [3 * n_fam]); None without."""
 
-    def __init__(self, stream, slot, out, n_fam, out_ss=None, filtered=False, metrics=False, base_metrics=False):
+    def __init__(self, stream, slot, out, n_fam, out_ss=None, filtered=False, metrics=False, base_metrics=False,
+                 overlap=False):
         self._stream, self._slot = stream, slot
         self.fam_fail = out.fam_fail[:n_fam]
         self.fam_filt = out.fam_filt[:n_fam] if filtered else None
         self.metrics = out.metrics if metrics else None
         self.base_metrics = out.base_metrics if base_metrics else None
+        self.fam_ovl = out.fam_ovl[:3 * n_fam] if overlap else None
         self.ds_len = out.ds_len[:2 * n_fam]
         self.bgzf_bytes, self.record_bytes, self.blocks = (int(x) for x in out.totals[:3])
         self.bgzf = out.blocks.array[:self.bgzf_bytes]
@@ -238,7 +247,12 @@ class DeviceStream:
     ``base_metrics`` (set per run too, --base_metrics_output): the device
     writer counts the per-base duplex QC tables (dcr_set_base_metrics) and
     ``result`` carries them as ``base_metrics``.  Device writer only, for the
-    same reason."""
+    same reason.
+
+    ``mate_overlap`` (set per run too, --mate_overlap): 0, params.OVL_MASK or
+    params.OVL_CONSENSUS.  The device writer reconciles the overlapping mates
+    (dcr_set_mate_overlap) and ``result`` carries ``fam_ovl``; on the host path
+    the caller does (native_io.apply_overlap)."""
 
     def __init__(self, ctx, n_slots=2, owns_ctx=False, device_writer=True, persistent=False):
         """``persistent``: ``close`` only drains the slots (the context and the
@@ -256,6 +270,7 @@ class DeviceStream:
         self.metrics = False
         self.base_tags = False
         self.base_metrics = False
+        self.mate_overlap = 0
         self.wouts_ss = None
         self.lib = _lib.load()
         self.n_slots = n_slots
@@ -291,12 +306,16 @@ class DeviceStream:
             filtered = self.filter is not None
             counted = bool(self.metrics)
             based = bool(self.base_metrics)
-            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered, counted, based)
+            ovl = int(self.mate_overlap or 0)
+            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered, counted, based, ovl != 0)
             # the context may serve other streams: its filter, metrics and tags are this stream's for this batch
             self.ctx.set_filter(self.filter)
             self.ctx.set_metrics(counted)
             self.ctx.set_base_tags(self.base_tags)
             self.ctx.set_base_metrics(based)
+            self.ctx.set_mate_overlap(ovl)
+            if ovl:
+                _lib._check(self.lib.dcr_slot_overlap_out(self.ctx._ctx, slot, wo.ovl.ptr))
             if based:
                 _lib._check(self.lib.dcr_slot_base_metrics_out(self.ctx._ctx, slot, wo.bmet.ptr))
             if counted:
@@ -322,11 +341,11 @@ class DeviceStream:
                                                          ctypes.byref(ms), ctypes.byref(self._wres),
                                                          ctypes.byref(self._wres_ss)))
                 self.busy[slot] = True
-                return (slot, s.n_fam, True, filtered, counted, based)
+                return (slot, s.n_fam, True, filtered, counted, based, ovl != 0)
             _lib._check(self.lib.dcr_submit_write(self.ctx._ctx, slot, ctypes.byref(self._b), ctypes.byref(m),
                                                   ctypes.byref(self._wres)))
             self.busy[slot] = True
-            return (slot, s.n_fam, False, filtered, counted, based)
+            return (slot, s.n_fam, False, filtered, counted, based, ovl != 0)
         out = self.outs[slot]
         out.ensure(4 * s.n_fam, s.ss_cols, 2 * s.n_fam, s.ds_cols, s.n_reads,
                    SS_FIELDS_FULL if self.ss_output else SS_FIELDS)
@@ -361,7 +380,7 @@ class DeviceStream:
                     grown = True
             if not grown:
                 _lib._check(rc)
-            return WriterResult(self, slot, wo, n_fam, ws, handle[3], handle[4], handle[5])
+            return WriterResult(self, slot, wo, n_fam, ws, handle[3], handle[4], handle[5], handle[6])
         slot = handle
         _lib._check(self.lib.dcr_wait(self.ctx._ctx, slot))
         self.busy[slot] = False
@@ -389,7 +408,7 @@ class DeviceStream:
             if o.mem is not None:
                 o.mem.free()
         for w in self.wouts + (self.wouts_ss or []):
-            for m in (w.small, w.blocks, w.filt, w.met, w.bmet):
+            for m in (w.small, w.blocks, w.filt, w.met, w.bmet, w.ovl):
                 if m is not None:
                     m.free()
         if self.owns_ctx:
@@ -404,6 +423,7 @@ class CallBackend:
         self.ss_output = False
         self.filter = None               # applied by the caller (native_io.apply_filter)
         self.metrics = False             # counted by the caller (native_io.metrics)
+        self.mate_overlap = 0            # applied by the caller (native_io.apply_overlap)
         self._res = {}
         self._k = 0
 

@@ -493,6 +493,62 @@ int dcr_set_base_metrics(dcr_ctx *ctx, int on);
  * complete when dcr_wait_write[_ss] returns.  NULL removes it. */
 int dcr_slot_base_metrics_out(dcr_ctx *ctx, int slot, dcr_base_metrics *pinned_dst);
 
+/* Overlapping mates (not a reference feature; the step that fgbio's
+ * overlapping-bases consensus or ClipBam --clip-overlapping-reads do on the
+ * written file: the rules below are the specification, fgbio was not run).
+ * The two duplex records 2f and 2f + 1 of a family are mates on the same
+ * reference (fam_tid[f]); where both have an aligned base on a reference
+ * position the molecule is reported twice.  With a mode set,
+ * dcr_submit_write[_ss] compares the two records of every family that does
+ * not fail at each such position and rewrites their seq / qual in the slot,
+ * after the QC tables are counted and before any filter, the formatters and
+ * the compressor.  No other field changes (length, CIGAR, position, flag, mate
+ * fields, TLEN, every tag with or without dcr_set_base_tags), and no
+ * single-strand record does.
+ *
+ * The map of a record, from what is written of it: start pos, CIGAR, and len
+ * clamped to [0, the record's region] (n_cig likewise).  The CIGAR is walked
+ * with SAM semantics in 64-bit arithmetic: M, = and X give n bases on n
+ * consecutive reference positions; I and S give n bases and no position; D
+ * and N give n positions and no base; H and P (and the unused operation
+ * codes) give neither.  A base index at or past len is not in the map.  This
+ * is not reconstruct_alignment's layout, and the stored column maps of the
+ * per-base filters are not used.
+ *
+ * For every reference position p in both maps, with base indices i0 / i1,
+ * (x, qx) = (seq0[i0], qual0[i0]) and (y, qy) = (seq1[i1], qual1[i1]), bytes
+ * compared as stored:
+ *   x == 'N' or y == 'N'   nothing changes; the position is not compared
+ *   x == y                 DCR_OVL_MASK: nothing changes
+ *                          DCR_OVL_CONSENSUS: both qualities min(qx + qy, 93)
+ *   x != y                 DCR_OVL_MASK: both bases 'N', each at min(its own
+ *                          quality, 2)
+ *                          DCR_OVL_CONSENSUS: qx > qy: both bases x at quality
+ *                          qx - qy; qy > qx: both y at qy - qx; qx == qy: both
+ *                          masked as DCR_OVL_MASK does
+ * Every result comes from the values before the step; a base has at most one
+ * reference position, so the pairs are independent.
+ *
+ * fam_ovl[3f .. 3f + 2]: compared (positions with both bases not 'N'),
+ * disagree (the compared positions with x != y), changed (bases, over both
+ * records, whose seq or qual byte changed); 0 0 0 for a failing family, which
+ * is not touched.  k_metrics and k_base_metrics run before the step and
+ * describe the consensus as called; k_base_filter and k_filter run after it,
+ * see the records as it left them and count by their own definitions.  The
+ * mode alone launches no filter and produces no fam_filt. */
+#define DCR_OVL_MASK 1
+#define DCR_OVL_CONSENSUS 2
+/* mode 0: off (the default; nothing is launched, copied, zeroed or allocated
+ * and no output byte changes); any value but 0, DCR_OVL_MASK and
+ * DCR_OVL_CONSENSUS is DCR_EARG.  Holds for the batches submitted after the
+ * call. */
+int dcr_set_mate_overlap(dcr_ctx *ctx, int mode);
+/* Where a slot's fam_ovl[3F] goes (pinned host memory, at least 3 * n_fam
+ * int32 of every batch submitted on the slot while a mode is set): copied with
+ * fam_fail, on the same stream and before the same event, so it is complete
+ * when dcr_wait_write[_ss] returns.  NULL removes it. */
+int dcr_slot_overlap_out(dcr_ctx *ctx, int slot, int32_t *fam_ovl);
+
 /* CPU restatement with the same contract (oracle/, test infrastructure):
    host pointers, single thread (or n_threads > 1) */
 int dcr_oracle_run(const dcr_params *params, const dcr_batch *in, dcr_out *ss, dcr_out *ds,

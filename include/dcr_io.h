@@ -275,6 +275,17 @@ int dcr_fmt_write_filt(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out 
 int dcr_fmt_write_ss_filt(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_out *ss, int32_t n_fam,
                           const int32_t *fam_filt);
 
+/* The overlapping mates on the host (include/dcr.h dcr_set_mate_overlap
+ * states the map and the rules; the device's k_mate_overlap gives the same
+ * bytes and words).  Compares the two duplex records of processed families
+ * [0, n_fam), none of which fails, at every reference position both cover and
+ * rewrites ds->seq / ds->qual IN PLACE (through the const pointers); mode is
+ * DCR_OVL_MASK or DCR_OVL_CONSENSUS.  fam_ovl[3f .. 3f + 2]: compared,
+ * disagree, changed.  To be called after dcr_fmt_metrics and before
+ * dcr_fmt_filter. */
+int dcr_fmt_mate_overlap(const dcr_host_batch *hb, const dcr_fmt_out *ds, int mode, int32_t n_fam,
+                         int32_t *fam_ovl);
+
 /* The consensus QC tables on the host (include/dcr.h dcr_metrics states the
  * definitions; the device's k_metrics gives the same words).  Adds the counts
  * of processed families [0, n_fam) into *m (the caller zeroes it), skipping
