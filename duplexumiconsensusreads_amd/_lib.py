@@ -56,6 +56,8 @@ EXPORTS = {
     "dcr_slot_base_metrics_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "dcr_set_mate_overlap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "dcr_slot_overlap_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "dcr_set_allele_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
+    "dcr_allele_counts_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     # include/dcr_inflate.h: BGZF inflate on the device
     "dcr_inflater_create": (ctypes.c_void_p, [ctypes.c_int]),
     "dcr_inflater_destroy": (None, [ctypes.c_void_p]),
@@ -135,6 +137,7 @@ class Context:
         self.base_tags = False
         self.base_metrics = False
         self.mate_overlap = 0
+        self.allele_sites = 0            # sites of the table on the context (set_allele_sites), 0: off
         if want_info:
             _check(lib.dcr_set_options(self._ctx, 1))
 
@@ -200,6 +203,29 @@ class Context:
             return
         _check(load().dcr_set_mate_overlap(self._ctx, mode))
         self.mate_overlap = mode
+
+    def set_allele_sites(self, keys, min_base_quality=0):
+        """The device writer counts the alleles at the sites ``keys``
+        (params.allele_keys; include/dcr.h dcr_set_allele_sites) into a fresh
+        zeroed table on the context, for the batches it takes from now on;
+        None or no keys: off.  Every call with keys starts a new table."""
+        n = 0 if keys is None else len(keys)
+        if n == 0:
+            if self.allele_sites:
+                _check(load().dcr_set_allele_sites(self._ctx, None, 0, 0))
+            self.allele_sites = 0
+            return
+        keys = np.ascontiguousarray(keys, np.int64)
+        _check(load().dcr_set_allele_sites(self._ctx, keys.ctypes.data, n, int(min_base_quality)))
+        self.allele_sites = n
+
+    def allele_counts(self):
+        """The table so far, uint64 [sites, 8] (dcr_allele_counts_fetch: waits
+        for the batches submitted so far; the table goes on accumulating)."""
+        from .params import ALLELE_COLS
+        out = np.zeros((max(self.allele_sites, 1), ALLELE_COLS), np.uint64)
+        _check(load().dcr_allele_counts_fetch(self._ctx, out.ctypes.data))
+        return out[:self.allele_sites]
 
     @property
     def stream(self):

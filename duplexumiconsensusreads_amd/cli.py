@@ -54,6 +54,14 @@ adds the qualities of agreeing bases (at most 93).  Only ``SEQ`` and ``QUAL`` of
 the duplex reads change; the step comes after the QC tables and before any
 ``--filter_*``.  Off by default; without it no output byte changes.
 
+``--allele_sites FILE --allele_counts_output FILE.tsv`` (not reference flags;
+each needs the other) count, per listed reference position, how many written
+families show A, C, G, T, N, a deletion or two disagreeing reads (include/dcr.h
+``dcr_set_allele_sites``): a family counts once where its two reads overlap.
+The records count as they are written, after ``--mate_overlap`` and every
+``--filter_*``; ``--allele_min_base_quality Q`` makes a base below Q count as
+N.  Off by default; no other output byte changes with them.
+
 Batches are pipelined: a thread ingests batch k+1 while the device runs batch
 k and the main thread writes batch k-1.
 
@@ -166,7 +174,20 @@ def parse_args(argv):
                     help="where the two duplex reads of a family cover the same reference position: 'mask' turns "
                          "disagreeing bases into 'N'; 'consensus' keeps the base of the higher quality at the "
                          "difference of the two and gives agreeing bases the sum (at most 93)")
-    return ap.parse_args(argv)
+    # not reference flags: duplex allele counts at given sites (include/dcr.h dcr_set_allele_sites)
+    ap.add_argument("--allele_sites", required=False, default=None, type=str, metavar="FILE",
+                    help="sites to count alleles at: lines name<TAB>pos (1-based) or BED name<TAB>start<TAB>end "
+                         "(0-based, every position of [start, end)); needs --allele_counts_output")
+    ap.add_argument("--allele_counts_output", required=False, default=None, type=str, metavar="FILE.tsv",
+                    help="per site of --allele_sites, how many written families show A, C, G, T, N, a deletion or "
+                         "two disagreeing reads (a family counts once where its two reads overlap) into FILE.tsv")
+    ap.add_argument("--allele_min_base_quality", required=False, default=0, metavar="Q",
+                    type=params_mod.allele_min_base_quality,
+                    help="for --allele_counts_output: a base below Q counts as N")
+    args = ap.parse_args(argv)
+    if (args.allele_sites is None) != (args.allele_counts_output is None):
+        raise ValueError("--allele_sites and --allele_counts_output need each other")
+    return args
 
 
 class ReferenceExit(SystemExit):
@@ -309,7 +330,7 @@ def gpu_inflate(device: int = 0):
 
 
 def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=False, base_tags=False,
-                base_metrics=False, mate_overlap=0):
+                base_metrics=False, mate_overlap=0, allele=None):
     """``ss_output``: this run also writes the single-strand records (a
     property of the run, set on the backend each time: the default backend
     is kept across runs).  ``flt``: this run's ConsensusFilter or None,
@@ -354,6 +375,11 @@ def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=Fa
         be.mate_overlap = mate_overlap or 0
     elif mate_overlap:
         raise ValueError("this backend cannot reconcile the overlapping mates")
+    # --allele_sites: (keys, min base quality) or None; set each time, so a kept backend starts a fresh table
+    if hasattr(be, "set_allele_sites"):
+        be.set_allele_sites(*(allele or (None,)))
+    elif allele:
+        raise ValueError("this backend cannot count the alleles")
     return be
 
 
@@ -406,6 +432,46 @@ def _finish_metrics(path, total, done, to_json=None):
             os.remove(path)
 
 
+def _check_allele_output(args, header, say=True):
+    """--allele_counts_output must name a .tsv file, as the metrics files name
+    .json ones; the sites of --allele_sites are read against the input's
+    ``header`` (a bad line is a ValueError before any file exists) and the
+    file is created here, before the pass.  Sets ``args.allele`` to (keys,
+    --allele_min_base_quality, reference names), or None without the option."""
+    args.allele = None
+    path = args.allele_counts_output
+    if path is None:
+        return
+    if not path.endswith(".tsv"):
+        if say:
+            print(OUTPUT_FORMAT_ERROR)
+        raise ReferenceExit(1)
+    refs = params_mod.header_references(header)
+    keys = params_mod.allele_keys(args.allele_sites, refs)
+    open(path, "a").close()
+    args.allele = (keys, args.allele_min_base_quality, refs)
+
+
+def _finish_allele(args, total, done):
+    """The run's table as TSV when it completed; otherwise no file, as the metrics."""
+    path = args.allele_counts_output
+    if path is None:
+        return
+    if done and total is not None and getattr(args, "allele", None) is not None:
+        with open(path, "w") as f:
+            f.write(params_mod.allele_tsv(args.allele[0], total, args.allele[2]))
+    else:
+        with contextlib.suppress(OSError):
+            os.remove(path)
+
+
+def _allele_summary(c, total):
+    """The summary's counters of a table (``_print_summary``)."""
+    if total is not None:
+        (c["allele_sites"], c["allele_covered"], c["allele_molecules"],
+         c["allele_discordant"]) = params_mod.allele_totals(total)
+
+
 def _raise_reference(kind: str, msg: str = ""):
     if kind == "exit":
         raise ReferenceExit(1)
@@ -442,6 +508,11 @@ class _Driver:
         self.metrics_total = np.zeros(params_mod.MET_WORDS, np.uint64) if args.metrics_output is not None else None
         self.base_metrics_total = (np.zeros(params_mod.BMET_WORDS, np.uint64)
                                    if args.base_metrics_output is not None else None)
+        # --allele_sites: (keys, min base quality); the table is summed here on the host path and
+        # fetched from the device writer's context once, after the last batch
+        al = getattr(args, "allele", None)
+        self.allele = None if al is None or len(al[0]) == 0 else (al[0], al[1])
+        self.allele_total = None if al is None else np.zeros((len(al[0]), params_mod.ALLELE_COLS), np.uint64)
 
     # -- stdout of one batch, in the reference's order --------------------------
     def _prints(self, hb, fail_f, kind, which, last_batch):
@@ -597,6 +668,9 @@ class _Driver:
             # after the tables (the consensus as called), before the filter (which sees what this leaves)
             ovl = native_io.apply_overlap(hb, ss, ds, self.overlap, fail_f) if self.overlap else None
             filt = native_io.apply_filter(hb, ss, ds, self.filter, fail_f) if self.filter is not None else None
+            if self.allele is not None and fail_f:
+                # the records as they are written: after the overlap step and the filter
+                native_io.allele_counts(hb, ds, self.allele[0], self.allele[1], fail_f, filt, self.allele_total)
             self.cons.write_consensus(hb, ss, ds, fail_f, filt)
             if self.sscs is not None:
                 self.sscs.write_consensus_ss(hb, ss, fail_f, filt)
@@ -740,11 +814,16 @@ class _Driver:
                     break
             self.finish(*pending, last_batch=True)
             pending = None
+            if self.allele is not None and getattr(self.backend, "device_writer", False):
+                self.allele_total = self.backend.allele_counts()
         finally:
             stop.set()
             free.put(None)
             th.join()
             t0 = time.perf_counter()
+            if self.allele is not None and getattr(self.backend, "device_writer", False):
+                with contextlib.suppress(Exception):    # a kept backend does not keep the table
+                    self.backend.set_allele_sites(None)
             self.backend.close()
             if hasattr(self.backend, "release"):
                 self.backend.release(batches)
@@ -784,15 +863,22 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
     _check_ss_output(args)
     ss_path = args.single_strand_output
     try:
-        _check_metrics_output(args)
+        _check_allele_output(args, ing.header)
+        try:
+            _check_metrics_output(args)
+        except BaseException:
+            _finish_allele(args, None, False)
+            raise
     except BaseException:
         ing.close()
         raise
     met_path, met_total, done = args.metrics_output, None, False
     bmet_path, bmet_total = args.base_metrics_output, None
+    al_total = None
     try:
         be = _as_backend(backend, params, args.device, ss_path is not None, ConsensusFilter.from_args(args),
-                         met_path is not None, args.per_base_tags, bmet_path is not None, args.mate_overlap)
+                         met_path is not None, args.per_base_tags, bmet_path is not None, args.mate_overlap,
+                         args.allele and args.allele[:2])
         cons, excl, unproc, *rest = _open_writers(
             [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
              "%s_filteredfamilies.bam" % consensus_filename[:-4]] + ([ss_path] if ss_path else []), ing.header, args,
@@ -800,6 +886,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
     except BaseException:
         _finish_metrics(met_path, None, False)      # no empty metrics file from a run that never started
         _finish_metrics(bmet_path, None, False)
+        _finish_allele(args, None, False)
         raise
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng.getstate())
@@ -821,6 +908,8 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
             stats.update(c)
         c.update(drv.filter_counts)
         c.update(drv.overlap_counts)
+        al_total = drv.allele_total
+        _allele_summary(c, al_total)
         if args.verbose:
             print("\n Input file has been completely read \n")
         _print_summary(c)
@@ -840,7 +929,10 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
                     try:
                         _finish_metrics(met_path, met_total, done)
                     finally:
-                        _finish_metrics(bmet_path, bmet_total, done, params_mod.base_metrics_json)
+                        try:
+                            _finish_metrics(bmet_path, bmet_total, done, params_mod.base_metrics_json)
+                        finally:
+                            _finish_allele(args, al_total, done)
         if stats is not None:
             stats["close_s"] = time.perf_counter() - t_close
             stats["close_writers_s"] = t_wclose - t_close
@@ -899,6 +991,10 @@ def _print_summary(c):
               % c["overlap_compared"])
         print("\n A total of %d of them held two different bases." % c["overlap_disagree"])
         print("\n A total of %d bases were changed where the reads of a pair overlap." % c["overlap_changed"])
+    if "allele_sites" in c:
+        # only with --allele_sites: the families that were written, each once per site
+        print("\n Allele counts at %d sites: %d sites covered, %d molecules counted, %d of them discordant."
+              % (c["allele_sites"], c["allele_covered"], c["allele_molecules"], c["allele_discordant"]))
 
 
 # -- sharded mode: one process per GPU over ranges of whole families ---------------
@@ -1004,7 +1100,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
                            ss_meta=len(parts) > 3)
     be = _as_backend(backend, params, device, len(parts) > 3, ConsensusFilter.from_args(args),
                      args.metrics_output is not None, args.per_base_tags, args.base_metrics_output is not None,
-                     args.mate_overlap)
+                     args.mate_overlap, args.allele and args.allele[:2])
     cons, excl, unproc, *rest = _open_writers(parts, header, args, ing)
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng_state)
@@ -1026,6 +1122,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
         res["counters"] = dict(ing.counters(), **drv.filter_counts, **drv.overlap_counts)
         res["metrics"] = drv.metrics_total
         res["base_metrics"] = drv.base_metrics_total
+        res["allele_counts"] = drv.allele_total
         res["stats"] = dict(drv.stats)
         res["stdout"] = out.getvalue()
         try:
@@ -1323,6 +1420,7 @@ def _main_sharded(args, params, backend, rng, stats, group):
             print(OUTPUT_FORMAT_ERROR)
         raise ReferenceExit(1)
     _check_ss_output(args, say=rank == 0)
+    _check_allele_output(args, header, say=rank == 0)   # every rank reads the sites: the ranks' tables line up
     _check_metrics_output(args, say=rank == 0)      # every rank: a bad path ends them all before any collective
     finals = [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
               "%s_filteredfamilies.bam" % consensus_filename[:-4]]
@@ -1416,9 +1514,18 @@ def _main_sharded(args, params, backend, rng, stats, group):
         for r in range(min(world, len(ranges))):
             for k, v in (results[r]["counters"] or {}).items():
                 tot[k] = tot.get(k, 0) + v
+        al_total = None
+        if args.allele is not None:
+            # integer sums too: a family is counted by the rank that writes it
+            al_total = np.zeros((len(args.allele[0]), params_mod.ALLELE_COLS), np.uint64)
+            for r in range(min(world, len(ranges))):
+                if results[r].get("allele_counts") is not None:
+                    al_total += results[r]["allele_counts"]
+            _allele_summary(tot, al_total)
         if args.verbose:
             print("\n Input file has been completely read \n")
         _print_summary(tot)
+        _finish_allele(args, al_total, True)
         if args.metrics_output is not None:
             # integer sums: the ranks' totals add up to the single-process run's
             met = np.zeros(params_mod.MET_WORDS, np.uint64)
@@ -1435,6 +1542,7 @@ def _main_sharded(args, params, backend, rng, stats, group):
         return 0
     _finish_metrics(args.metrics_output, None, False)
     _finish_metrics(args.base_metrics_output, None, False)
+    _finish_allele(args, None, False)
     st, ea = results[fail]["status"], results[fail]["exc_args"]
     if st == "exit":
         raise ReferenceExit(*ea)

@@ -366,6 +366,12 @@ struct dcr_ctx {
     bool base_tags = false;          // dcr_set_base_tags
     bool base_metrics = false;       // dcr_set_base_metrics
     int mate_overlap = 0;            // dcr_set_mate_overlap: 0 off, DCR_OVL_MASK, DCR_OVL_CONSENSUS
+    // dcr_set_allele_sites: the sorted keys and the table [n_allele][DCR_ALLELE_COLS] every slot's
+    // k_allele_counts adds into; all null / 0: off
+    int64_t *d_allele_keys = nullptr;
+    unsigned long long *d_allele_tab = nullptr;
+    int64_t n_allele = 0;
+    int allele_min_q = 0;
     // the column maps of the batch being submitted (submit_write sets them around its
     // dcr_run_batch when a base filter, the per-base tags or the base metrics are on); all null otherwise
     dcr::BaseMap bmap{};
@@ -728,6 +734,8 @@ void dcr_destroy(dcr_ctx *c) {
     if (c->d_r2tab) (void)hipFree(c->d_r2tab);
     if (c->d_e1000) (void)hipFree(c->d_e1000);
     if (c->d_wtab) (void)hipFree(c->d_wtab);
+    if (c->d_allele_keys) (void)hipFree(c->d_allele_keys);
+    if (c->d_allele_tab) (void)hipFree(c->d_allele_tab);
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1202,6 +1210,14 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
                                 wb.base_masked};
             hipLaunchKernelGGL(dcrw::k_filter, dim3(gf), dim3(256), 0, c->stream, Fa);
         }
+        if (c->n_allele) {
+            // one wave per family, after the last kernel that rewrites or drops a duplex record: it
+            // counts the records as they will be written, into the context's table
+            dcrw::AlleleArgs Aa{dout[1], db.ds_col_off, wb.fam_fail, wb.fam_filt, wb.fam_tid, c->d_allele_keys,
+                                c->d_allele_tab, c->n_allele, (int32_t)F, c->allele_min_q};
+            const unsigned ga = (unsigned)std::max<int64_t>(1, std::min<int64_t>((F + 3) / 4, (int64_t)c->n_cu * 8));
+            hipLaunchKernelGGL(dcrw::k_allele_counts, dim3(ga), dim3(256), 0, c->stream, Aa);
+        }
         const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((2 * F + 3) / 4, (int64_t)c->n_cu * 8));
         if (btags)
             hipLaunchKernelGGL(dcrw::k_fmt_size_tags, dim3(g), dim3(256), 0, c->stream, A);
@@ -1364,6 +1380,62 @@ int dcr_slot_overlap_out(dcr_ctx *c, int slot, int32_t *fam_ovl) {
     if (!c || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
     if (c->slots[slot].busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
     c->slots[slot].h_fam_ovl = fam_ovl;
+    return DCR_OK;
+}
+
+int dcr_set_allele_sites(dcr_ctx *c, const int64_t *keys, int64_t n, int min_base_quality) {
+    if (!c) return fail(DCR_EARG, "NULL context");
+    if (!keys || n == 0) {
+        if (c->n_allele) {
+            // the table may still be counted into: the batches in flight first
+            HIP_TRY(hipSetDevice(c->device));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            (void)hipFree(c->d_allele_keys);
+            (void)hipFree(c->d_allele_tab);
+        }
+        c->d_allele_keys = nullptr;
+        c->d_allele_tab = nullptr;
+        c->n_allele = 0;
+        c->allele_min_q = 0;
+        return DCR_OK;
+    }
+    if (n < 0 || n > DCR_ALLELE_MAX_SITES) return fail(DCR_EARG, "allele sites: n outside [0, DCR_ALLELE_MAX_SITES]");
+    if (min_base_quality < 0) return fail(DCR_EARG, "allele sites: min_base_quality < 0");
+    for (int64_t i = 0; i < n; ++i) {
+        if (keys[i] < 0 || (keys[i] & 0x80000000ll)) return fail(DCR_EARG, "allele sites: tid or pos outside [0, 2^31)");
+        if (i && keys[i] <= keys[i - 1]) return fail(DCR_EARG, "allele sites: keys must be strictly increasing");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int64_t *dk = nullptr;
+    unsigned long long *dt = nullptr;
+    const size_t tab_bytes = (size_t)n * DCR_ALLELE_COLS * sizeof(unsigned long long);
+    hipError_t e = hipMalloc(&dk, (size_t)n * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc(&dt, tab_bytes);
+    if (e == hipSuccess) e = hipMemcpy(dk, keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dt, 0, tab_bytes);
+    if (e != hipSuccess) {
+        if (dk) (void)hipFree(dk);
+        if (dt) (void)hipFree(dt);
+        return fail(DCR_EHIP, hipGetErrorString(e));
+    }
+    if (c->d_allele_keys) (void)hipFree(c->d_allele_keys);
+    if (c->d_allele_tab) (void)hipFree(c->d_allele_tab);
+    c->d_allele_keys = dk;
+    c->d_allele_tab = dt;
+    c->n_allele = n;
+    c->allele_min_q = std::min(min_base_quality, 256);
+    return DCR_OK;
+}
+
+int dcr_allele_counts_fetch(dcr_ctx *c, uint64_t *dst) {
+    if (!c || !dst) return fail(DCR_EARG, "NULL argument");
+    if (!c->n_allele) return fail(DCR_EARG, "no allele sites are set (dcr_set_allele_sites)");
+    HIP_TRY(hipSetDevice(c->device));
+    // every slot's kernels run on the context's stream
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(dst, c->d_allele_tab, (size_t)c->n_allele * DCR_ALLELE_COLS * sizeof(uint64_t),
+                      hipMemcpyDeviceToHost));
     return DCR_OK;
 }
 

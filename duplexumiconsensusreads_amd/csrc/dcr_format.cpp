@@ -732,6 +732,86 @@ int dcr_fmt_mate_overlap(const dcr_host_batch *hb, const dcr_fmt_out *ds, int mo
     return DCR_IO_OK;
 }
 
+// the allele counts of include/dcr.h (dcr_set_allele_sites), as dcr_writer.hip's k_allele_counts
+// counts them; here site by site: both records' calls from a walk of their CIGARs
+static int ac_base(const MoRec &R, int64_t i, int min_q) {
+    if ((int)R.qual[i] < min_q) return 4;
+    const uint8_t b = R.seq[i];
+    return b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : 4;
+}
+
+// the call of a record at p (-1: none); *end, when given, receives the position after the walk
+static int ac_call_at(const MoRec &R, int64_t p, int min_q, int64_t *end = nullptr) {
+    int64_t rp = R.pos, bi = 0;
+    int call = -1;
+    for (int64_t k = 0; k < R.ncig && bi < R.len; ++k) {
+        const uint32_t v = R.cig[k];
+        const int64_t n = v >> 4;
+        const uint32_t op = v & 15u;
+        if (op == 0u || op == 7u || op == 8u) {
+            if (p >= rp && p < rp + n && bi + (p - rp) < R.len) call = ac_base(R, bi + (p - rp), min_q);
+            rp += n;
+            bi += n;
+        } else if (op == 2u) {
+            if (p >= rp && p < rp + n) call = 5;
+            rp += n;
+        } else if (op == 1u || op == 4u) {
+            bi += n;
+        } else if (op == 3u) {
+            rp += n;
+        }
+    }
+    if (end) *end = rp;
+    return call;
+}
+
+int dcr_fmt_allele_counts(const dcr_host_batch *hb, const dcr_fmt_out *ds, const int64_t *keys, int64_t n_keys,
+                          int min_base_quality, int32_t n_fam, const int32_t *fam_filt, uint64_t *table) {
+    if (!hb || !ds || !keys || !table || n_keys <= 0 || n_keys > DCR_ALLELE_MAX_SITES || min_base_quality < 0 ||
+        n_fam < 0 || n_fam > hb->n_fam)
+        return fail(DCR_IO_EARG, "bad arguments");
+    for (int64_t i = 0; i < n_keys; ++i)
+        if (keys[i] < 0 || (keys[i] & 0x80000000ll) || (i && keys[i] <= keys[i - 1]))
+            return fail(DCR_IO_EARG, "allele sites: keys must be tid << 32 | pos, strictly increasing");
+    auto clampi = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : v > hi ? hi : v; };
+    const int64_t pos_end = (int64_t)1 << 31;
+    for (int32_t f = 0; f < n_fam; ++f) {
+        if (fam_filt && (fam_filt[f] & 0xff)) continue;
+        const int64_t tid = hb->fam_tid[f];
+        if (tid < 0) continue;
+        MoRec R[2];
+        int64_t end[2];
+        for (int j = 0; j < 2; ++j) {
+            const int32_t k = 2 * f + j;
+            const int64_t ro = hb->ds_col_off[k], room = hb->ds_col_off[k + 1] - ro;
+            R[j] = MoRec{ds->cigar + ro, const_cast<uint8_t *>(ds->seq) + ro, const_cast<uint8_t *>(ds->qual) + ro,
+                         clampi(ds->len[k], room), clampi(ds->n_cig[k], room), ds->pos[k]};
+            (void)ac_call_at(R[j], 0, 0, &end[j]);
+        }
+        const int64_t lo = clampi(std::min(R[0].pos, R[1].pos), pos_end), hi = clampi(std::max(end[0], end[1]), pos_end);
+        const int64_t *a = std::lower_bound(keys, keys + n_keys, (tid << 32) + lo);
+        const int64_t *b = std::lower_bound(a, keys + n_keys, (tid << 32) + hi);
+        for (const int64_t *s = a; s < b; ++s) {
+            const int64_t p = *s - (tid << 32);
+            const int c0 = ac_call_at(R[0], p, min_base_quality), c1 = ac_call_at(R[1], p, min_base_quality);
+            if (c0 < 0 && c1 < 0) continue;
+            int col;
+            if (c1 < 0 || c0 == c1)
+                col = c0;
+            else if (c0 < 0 || c0 == 4)
+                col = c1;
+            else if (c1 == 4)
+                col = c0;
+            else
+                col = 6;
+            uint64_t *row = table + (s - keys) * DCR_ALLELE_COLS;
+            ++row[col];
+            if (c0 >= 0 && c1 >= 0) ++row[7];
+        }
+    }
+    return DCR_IO_OK;
+}
+
 // the tables of include/dcr.h (dcr_metrics), as dcr_writer.hip's k_metrics counts them
 static int met_err_bin(double E) {
     // one double multiply (built with -ffp-contract=off); NaN fails both compares

@@ -125,6 +125,20 @@ struct MateOverlapArgs {
     int32_t mode;                   // DCR_OVL_MASK or DCR_OVL_CONSENSUS
 };
 
+// the allele counts at given sites (k_allele_counts, dcr_set_allele_sites)
+struct AlleleArgs {
+    dcr_out ds;                     // device kernel outputs, as the filters left them; read only
+    const int64_t *ds_col_off;      // [2F+1]
+    const int32_t *fam_fail;        // [F] from k_famfail
+    const int32_t *fam_filt;        // [F] from k_filter, or null without a filter
+    const int32_t *fam_tid;         // [F]
+    const int64_t *keys;            // [n_keys] tid << 32 | pos, strictly increasing
+    unsigned long long *table;      // [n_keys][DCR_ALLELE_COLS], the context's
+    int64_t n_keys;
+    int32_t n_fam;
+    int32_t min_q;                  // a base below it calls N
+};
+
 struct DflArgs {
     const uint8_t *stream;
     const int64_t *stream_bytes;    // device scalar (rec_off[2F])
@@ -158,6 +172,7 @@ __global__ void k_fmt_size_ss_tags(FmtSsArgs A);
 __global__ void k_fmt_write_ss_tags(FmtSsTagArgs T);
 __global__ void k_base_metrics(BaseMetricsArgs A);
 __global__ void k_mate_overlap(MateOverlapArgs A);
+__global__ void k_allele_counts(AlleleArgs A);
 __global__ void k_deflate(DflArgs D);
 __global__ void k_compact(CompactArgs C);
 

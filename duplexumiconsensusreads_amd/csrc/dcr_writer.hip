@@ -2036,4 +2036,159 @@ __global__ __launch_bounds__(256) void k_mate_overlap(MateOverlapArgs A) {
     }
 }
 
+// ---- the allele counts at given sites (dcr_set_allele_sites; include/dcr.h
+// states the map, the calls and the table).  One wave per family in 256-lane
+// blocks, k_filter's grid; runs after the filters and before k_fmt_size, reads
+// the duplex records as they will be written and writes nothing but the
+// context's table.
+//
+// The work follows the sites hit, never the bases or the length of a run: the
+// wave first looks the family's whole span [min pos, max end) up in the sorted
+// keys (two lower bounds, wave-uniform: the wave index comes from
+// readfirstlane, so the keys' loads and every branch on them are the whole
+// wave's); a family that touches no site ends there.  Then it walks mate 1's
+// CIGAR run by run; for each M / = / X / D run two lower bounds inside the
+// range found give the sites of the run, and the lanes stride them.  A lane
+// has its own record's call by subtraction (base index = the run's first base
+// + p - the run's first position) and the other record's from a walk of that
+// record's CIGAR (ac_call_at; a duplex CIGAR is a few operations).  Mate 2's
+// runs follow in the same way and count only where mate 1 has no call.  A
+// (family, site) pair belongs to exactly one lane, so the table is the only
+// shared state: one 64-bit atomic add on the call's column, one on `both`
+// where both records call.  No LDS, no barrier.
+constexpr int64_t kAcPosEnd = (int64_t)1 << 31;     // a site's pos lies below it
+
+// first index in [lo, hi) whose key is not below `key`
+__device__ __forceinline__ int64_t ac_lower(const int64_t *keys, int64_t lo, int64_t hi, int64_t key) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int64_t ac_clip(int64_t p) { return p < 0 ? 0 : p > kAcPosEnd ? kAcPosEnd : p; }
+
+// the call of base i of a record (i inside the map)
+__device__ __forceinline__ int ac_base(const MoRec &R, int64_t i, uint32_t min_q) {
+    const uint32_t b = R.seq[i];
+    if ((uint32_t)R.qual[i] < min_q) return 4;
+    return b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : 4;
+}
+
+// the call of a record at reference position p, -1 for none
+__device__ __forceinline__ int ac_call_at(const MoRec &R, int64_t p, uint32_t min_q) {
+    int64_t rp = R.pos, bi = 0;
+    for (int64_t k = 0; k < R.ncig && bi < R.len && rp <= p; ++k) {
+        const uint32_t v = R.cig[k];
+        const int64_t n = v >> 4;
+        const uint32_t op = v & 15u;
+        if (op == 0u || op == 7u || op == 8u) {
+            if (p < rp + n) return bi + (p - rp) < R.len ? ac_base(R, bi + (p - rp), min_q) : -1;
+            rp += n;
+            bi += n;
+        } else if (op == 2u) {
+            if (p < rp + n) return 5;
+            rp += n;
+        } else if (op == 1u || op == 4u) {
+            bi += n;
+        } else if (op == 3u) {
+            rp += n;
+        }                   // H, P and the unused codes: neither
+    }
+    return -1;
+}
+
+// the reference position after the last operation of the map (no less than the map's end)
+__device__ __forceinline__ int64_t ac_end(const MoRec &R) {
+    int64_t rp = R.pos, bi = 0;
+    for (int64_t k = 0; k < R.ncig && bi < R.len; ++k) {
+        const uint32_t v = R.cig[k];
+        const int64_t n = v >> 4;
+        const uint32_t op = v & 15u;
+        if (op == 0u || op == 7u || op == 8u) {
+            rp += n;
+            bi += n;
+        } else if (op == 1u || op == 4u) {
+            bi += n;
+        } else if (op == 2u || op == 3u) {
+            rp += n;
+        }
+    }
+    return rp;
+}
+
+__device__ __forceinline__ int ac_molecule(int c0, int c1) {
+    if (c1 < 0 || c0 == c1) return c0;
+    if (c0 < 0) return c1;
+    if (c0 == 4) return c1;
+    if (c1 == 4) return c0;
+    return 6;
+}
+
+// the runs of record R with a call, the sites [s_lo, s_hi) of the family's span strided by the
+// lanes; O is the family's other record.  second: R is mate 2, whose sites count only where
+// mate 1 (O) has no call.
+__device__ __forceinline__ void ac_runs(const AlleleArgs &A, const MoRec &R, const MoRec &O, bool second, int64_t base,
+                                        int64_t s_lo, int64_t s_hi) {
+    int64_t rp = R.pos, bi = 0;
+    for (int64_t k = 0; k < R.ncig && bi < R.len && s_lo < s_hi; ++k) {
+        const uint32_t v = R.cig[k];
+        const int64_t n = v >> 4;
+        const uint32_t op = v & 15u;
+        const bool m = op == 0u || op == 7u || op == 8u;
+        if (m || op == 2u) {
+            const int64_t left = R.len - bi;
+            const int64_t ne = m && n > left ? left : n;
+            const int64_t a = ac_lower(A.keys, s_lo, s_hi, base + ac_clip(rp));
+            const int64_t b = ac_lower(A.keys, a, s_hi, base + ac_clip(rp + ne));
+            for (int64_t s = a + lane_id(); s < b; s += kW) {
+                const int64_t p = A.keys[s] - base;
+                const int own = m ? ac_base(R, bi + (p - rp), (uint32_t)A.min_q) : 5;
+                const int oth = ac_call_at(O, p, (uint32_t)A.min_q);
+                unsigned long long *row = A.table + s * DCR_ALLELE_COLS;
+                if (second) {
+                    if (oth < 0) atomicAdd(row + own, 1ull);
+                } else {
+                    atomicAdd(row + ac_molecule(own, oth), 1ull);
+                    if (oth >= 0) atomicAdd(row + 7, 1ull);
+                }
+            }
+            s_lo = b;           // the runs' positions ascend
+            rp += n;
+            if (m) bi += n;
+        } else if (op == 1u || op == 4u) {
+            bi += n;
+        } else if (op == 3u) {
+            rp += n;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_allele_counts(AlleleArgs A) {
+    const int64_t wpb = blockDim.x / kW;
+    const int64_t wave = (int64_t)blockIdx.x * wpb + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kW));
+    const int64_t nw = (int64_t)gridDim.x * wpb;
+    for (int64_t f = wave; f < A.n_fam; f += nw) {
+        if (A.fam_fail[f] != 0 || (A.fam_filt && (A.fam_filt[f] & 0xff))) continue;
+        const int64_t tid = A.fam_tid[f];
+        if (tid < 0) continue;
+        MoRec R0, R1;
+        mo_rec(A.ds, A.ds_col_off, 2 * f, R0);
+        mo_rec(A.ds, A.ds_col_off, 2 * f + 1, R1);
+        const int64_t e0 = ac_end(R0), e1 = ac_end(R1);
+        const int64_t lo = ac_clip(R0.pos < R1.pos ? R0.pos : R1.pos), hi = ac_clip(e0 > e1 ? e0 : e1);
+        if (lo >= hi) continue;
+        const int64_t base = tid << 32;
+        const int64_t s_lo = ac_lower(A.keys, 0, A.n_keys, base + lo);
+        const int64_t s_hi = ac_lower(A.keys, s_lo, A.n_keys, base + hi);
+        if (s_lo == s_hi) continue;         // the common case of a sparse panel: one search, no walk
+        ac_runs(A, R0, R1, false, base, s_lo, s_hi);
+        ac_runs(A, R1, R0, true, base, s_lo, s_hi);
+    }
+}
+
 }  // namespace dcrw

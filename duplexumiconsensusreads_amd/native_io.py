@@ -106,6 +106,7 @@ def load():
             "dcr_fmt_filter": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
             "dcr_fmt_metrics": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
             "dcr_fmt_mate_overlap": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+            "dcr_fmt_allele_counts": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _i32, _i32, _vp, _vp]),
             "dcr_fmt_write_filt": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
             "dcr_fmt_write_ss_filt": (_i32, [_vp, _vp, _vp, _i32, _vp]),
             "dcr_synth_write": (_i32, [_vp, _vp, _i32]),
@@ -459,6 +460,28 @@ def apply_overlap(hb: HostBatch, ss: FmtOut, ds: FmtOut, mode: int, n_fam: int) 
     if load().dcr_fmt_mate_overlap(ctypes.byref(hb.s), ctypes.byref(ds), int(mode), n_fam, out.ctypes.data) != 0:
         raise _err("mate overlap")
     return out[:3 * n_fam]
+
+
+def allele_counts(hb: HostBatch, ds: FmtOut, keys, min_base_quality: int, n_fam: int, fam_filt=None,
+                  table=None) -> np.ndarray:
+    """dcr_fmt_allele_counts: the allele counts (include/dcr.h
+    dcr_set_allele_sites) of processed families [0, n_fam), none of which
+    fails, at the sites ``keys`` (params.allele_keys: int64, strictly
+    increasing), added into ``table`` (uint64 [len(keys), 8]; None: a new
+    zeroed one) and returned.  ``fam_filt`` (apply_filter): the families it
+    drops are skipped.  To be called after ``apply_overlap`` and
+    ``apply_filter``: it counts the records as they are written."""
+    from .params import ALLELE_COLS
+    keys = np.ascontiguousarray(keys, np.int64)
+    if table is None:
+        table = np.zeros((len(keys), ALLELE_COLS), np.uint64)
+    assert table.dtype == np.uint64 and table.shape == (len(keys), ALLELE_COLS) and table.flags.c_contiguous
+    ff = None if fam_filt is None else np.ascontiguousarray(fam_filt, np.int32)
+    if load().dcr_fmt_allele_counts(ctypes.byref(hb.s), ctypes.byref(ds), keys.ctypes.data, len(keys),
+                                    int(min_base_quality), n_fam, ff.ctypes.data if ff is not None else None,
+                                    table.ctypes.data) != 0:
+        raise _err("allele counts")
+    return table
 
 
 def metrics(hb: HostBatch, ss: FmtOut, ds: FmtOut, n_fam: int, fam_fail=None) -> np.ndarray:

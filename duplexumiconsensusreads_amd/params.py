@@ -378,6 +378,116 @@ def mate_overlap(text):
     return OVL_MODES[text]
 
 
+# ---- allele counts at given sites (include/dcr.h dcr_set_allele_sites; --allele_sites) ----
+ALLELE_COLS = 8
+ALLELE_MAX_SITES = 1 << 24
+ALLELE_NAMES = ("A", "C", "G", "T", "N", "del", "discordant", "both")
+ALLELE_HEADER = "#chrom\tpos\t" + "\t".join(ALLELE_NAMES) + "\tdepth\n"
+
+
+def allele_min_base_quality(text):
+    """``--allele_min_base_quality``: an int >= 0."""
+    v = int(text)
+    if v < 0:
+        raise ValueError("--allele_min_base_quality must be >= 0")
+    return v
+
+
+def header_references(header: bytes):
+    """The reference names of a BAM header as stored (magic, text, references)."""
+    if header[:4] != b"BAM\1":
+        raise ValueError("not a BAM header")
+    (l_text,) = struct.unpack_from("<i", header, 4)
+    p = 8 + l_text
+    (n_ref,) = struct.unpack_from("<i", header, p)
+    p += 4
+    names = []
+    for _ in range(n_ref):
+        (ln,) = struct.unpack_from("<i", header, p)
+        names.append(header[p + 4:p + 4 + ln - 1].decode("latin-1"))
+        p += 4 + ln + 4
+    return names
+
+
+def allele_keys(path, references):
+    """The sites of an ``--allele_sites`` file as the keys dcr_set_allele_sites
+    takes: int64 ``tid << 32 | pos`` (pos 0-based), sorted by (tid, pos),
+    duplicates merged.  Empty lines and lines starting with '#' are ignored;
+    ``name<TAB>pos`` is one site, pos 1-based; ``name<TAB>start<TAB>end[...]``
+    is BED, every position of [start, end), 0-based.  ``references``: the
+    names of the input header, whose index is the tid.  A line that is
+    neither, names no reference or holds a position outside the reference
+    coordinates is a ValueError naming the line; so are more than
+    ALLELE_MAX_SITES sites."""
+    tid_of = {}
+    for i, name in enumerate(references):
+        tid_of.setdefault(name, i)
+    spans = []
+    with open(path, "r", encoding="latin-1") as f:
+        for no, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            where = "%s line %d" % (path, no)
+            cols = line.split("\t")
+            if len(cols) < 2:
+                raise ValueError("%s: expected name<TAB>pos or name<TAB>start<TAB>end" % where)
+            if cols[0] not in tid_of:
+                raise ValueError("%s: %r is not a reference of the input header" % (where, cols[0]))
+            try:
+                nums = [int(c) for c in cols[1:3]]
+            except ValueError:
+                raise ValueError("%s: a position is not an integer" % where) from None
+            if len(nums) == 1:
+                start, end = nums[0] - 1, nums[0]
+                if start < 0:
+                    raise ValueError("%s: a 1-based position must be at least 1" % where)
+            else:
+                start, end = nums
+                if start < 0:
+                    raise ValueError("%s: negative start" % where)
+                if end <= start:
+                    raise ValueError("%s: end must be above start" % where)
+            if end > (1 << 31):
+                raise ValueError("%s: position beyond 2^31" % where)
+            spans.append((tid_of[cols[0]], start, end))
+    spans.sort()
+    merged = []
+    for tid, start, end in spans:
+        if merged and merged[-1][0] == tid and start <= merged[-1][2]:
+            merged[-1][2] = max(merged[-1][2], end)
+        else:
+            merged.append([tid, start, end])
+    n = sum(end - start for _, start, end in merged)
+    if n > ALLELE_MAX_SITES:
+        raise ValueError("%s: %d sites, more than %d" % (path, n, ALLELE_MAX_SITES))
+    if not merged:
+        return np.zeros(0, np.int64)
+    return np.concatenate([(np.int64(tid) << np.int64(32)) + np.arange(start, end, dtype=np.int64)
+                           for tid, start, end in merged])
+
+
+def allele_tsv(keys, table, references) -> str:
+    """The ``--allele_counts_output`` file of a table (uint64 [len(keys), 8]):
+    the header line, then one line per site in the keys' order with pos 1-based
+    and depth the sum of the seven call columns; plain decimal integers, so the
+    same counters always give the same bytes."""
+    keys = np.asarray(keys, np.int64)
+    table = np.asarray(table, np.uint64).reshape(len(keys), ALLELE_COLS)
+    depth = table[:, :7].sum(axis=1, dtype=np.uint64)
+    out = [ALLELE_HEADER]
+    for k, row, d in zip(keys.tolist(), table.tolist(), depth.tolist()):
+        out.append("%s\t%d\t%s\t%d\n" % (references[k >> 32], (k & 0xffffffff) + 1, "\t".join(map(str, row)), d))
+    return "".join(out)
+
+
+def allele_totals(table):
+    """(sites, sites with depth > 0, molecules counted, discordant) of a table: the summary's line."""
+    table = np.asarray(table, np.uint64).reshape(-1, ALLELE_COLS)
+    depth = table[:, :7].sum(axis=1, dtype=np.uint64)
+    return len(table), int((depth > 0).sum()), int(depth.sum()), int(table[:, 6].sum())
+
+
 @dataclasses.dataclass(frozen=True)
 class ConsensusFilter:
     """The ``--filter_*`` options, parsed; None = that rule is off."""

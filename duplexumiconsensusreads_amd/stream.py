@@ -252,7 +252,12 @@ class DeviceStream:
     ``mate_overlap`` (set per run too, --mate_overlap): 0, params.OVL_MASK or
     params.OVL_CONSENSUS.  The device writer reconciles the overlapping mates
     (dcr_set_mate_overlap) and ``result`` carries ``fam_ovl``; on the host path
-    the caller does (native_io.apply_overlap)."""
+    the caller does (native_io.apply_overlap).
+
+    ``set_allele_sites`` (called per run too, --allele_sites): the device
+    writer counts the alleles at the sites into a table on the context
+    (dcr_set_allele_sites), which ``allele_counts`` fetches; on the host path
+    the caller counts (native_io.allele_counts)."""
 
     def __init__(self, ctx, n_slots=2, owns_ctx=False, device_writer=True, persistent=False):
         """``persistent``: ``close`` only drains the slots (the context and the
@@ -271,6 +276,7 @@ class DeviceStream:
         self.base_tags = False
         self.base_metrics = False
         self.mate_overlap = 0
+        self.allele = None               # (keys, min base quality) of set_allele_sites, or None
         self.wouts_ss = None
         self.lib = _lib.load()
         self.n_slots = n_slots
@@ -286,6 +292,18 @@ class DeviceStream:
             return spare.pop()
         return native_io.HostBatch(reads=reads, alloc=pinned_allocator(self.lib, self._pins),
                                    ss_meta=self.ss_output)
+
+    def set_allele_sites(self, keys, min_base_quality=0):
+        """``keys``: params.allele_keys' sites, or None (off).  On the device
+        writer every call with keys starts a fresh zeroed table on the context,
+        which the batches submitted from now on count into."""
+        self.allele = None if keys is None or len(keys) == 0 else (keys, int(min_base_quality))
+        if self.device_writer:
+            self.ctx.set_allele_sites(*(self.allele or (None,)))
+
+    def allele_counts(self):
+        """The device writer's table so far (uint64 [sites, 8]); waits for the batches submitted."""
+        return self.ctx.allele_counts()
 
     def release(self, batches):
         """Host batches a run is done with, kept for the next run (persistent)."""
@@ -424,11 +442,15 @@ class CallBackend:
         self.filter = None               # applied by the caller (native_io.apply_filter)
         self.metrics = False             # counted by the caller (native_io.metrics)
         self.mate_overlap = 0            # applied by the caller (native_io.apply_overlap)
+        self.allele = None               # counted by the caller (native_io.allele_counts)
         self._res = {}
         self._k = 0
 
     def host_batch(self, reads=1 << 20):
         return native_io.HostBatch(reads=reads, ss_meta=self.ss_output)
+
+    def set_allele_sites(self, keys, min_base_quality=0):
+        self.allele = None if keys is None or len(keys) == 0 else (keys, int(min_base_quality))
 
     def submit(self, hb):
         ss, ds, info = self.fn(hb.packed(), self.params)

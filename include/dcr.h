@@ -549,6 +549,65 @@ int dcr_set_mate_overlap(dcr_ctx *ctx, int mode);
  * when dcr_wait_write[_ss] returns.  NULL removes it. */
 int dcr_slot_overlap_out(dcr_ctx *ctx, int slot, int32_t *fam_ovl);
 
+/* Allele counts at given sites (not a reference feature; what a molecule-aware
+ * pileup of the written file would count: the rules below are the
+ * specification, no pileup tool was run).  With sites set,
+ * dcr_submit_write[_ss] counts, for every site and over the families that are
+ * written, which allele the molecule shows there.  A molecule is a family, not
+ * a record: where both duplex records cover a site they give one count.
+ *
+ * Which records count: the two duplex records 2f and 2f + 1 of a family f with
+ * fam_fail[f] == 0 that no filter rule dropped (fam_filt[f] & 0xff == 0 where a
+ * filter is set), as they are written: after k_mate_overlap, k_base_filter and
+ * k_filter, before the formatters.  No single-strand record counts.  A site
+ * (tid, pos) matches a family only when tid == fam_tid[f].
+ *
+ * The map of a record is the one of dcr_set_mate_overlap above (pos, CIGAR,
+ * len and n_cig clamped to the record's region, 64-bit arithmetic), with one
+ * addition: a D run gives the call `del` on each of its positions.  N runs
+ * give positions without a call; I and S give bases without a position; H and
+ * P give neither.  The walk ends where that one ends: at the last operation,
+ * or once the base index has reached len (an operation after the last base of
+ * the map, a D run included, gives nothing).
+ *
+ * The call of a record at position p:
+ *   none    the map has nothing at p
+ *   5 del   p lies in a D run
+ *   else from the base byte as stored: 'A' 'C' 'G' 'T' give 0 1 2 3, any other
+ *           byte 4 (N); a base whose qual < min_base_quality gives 4 too
+ * The molecule's call from the calls c0, c1 of its two records:
+ *   one of them present            that call
+ *   both present and equal         that call
+ *   exactly one of them 4 (N)      the other (a del too)
+ *   otherwise                      6 (discordant)
+ * table[i][0..6] count the molecules by that call at site i (A C G T N del
+ * discordant); table[i][7] (both) counts the molecules whose two records both
+ * have a call there, whatever it is: how often a plain pileup would have
+ * counted the molecule twice.  So every family adds exactly one to one of the
+ * columns 0..6 of every site either record covers, and nothing elsewhere.
+ *
+ * keys[i] = (int64_t)tid << 32 | pos with pos 0-based, 0 <= tid, pos < 2^31,
+ * strictly increasing, 0 < n <= DCR_ALLELE_MAX_SITES; anything else is
+ * DCR_EARG and leaves the state as it was.  n == 0 or keys == NULL turns the
+ * feature off and frees the table: the default, in which nothing is
+ * allocated, launched, copied or zeroed and no output byte changes.  n > 0
+ * waits for the batches in flight, uploads the keys and allocates and zeroes a
+ * device table uint64[n][8] that lives on the context, not on a slot (a panel
+ * can hold millions of sites; a copy per batch would cost more than the
+ * kernel): every call gives a fresh table, also with the keys of the last one.
+ * The table accumulates over every dcr_submit_write[_ss] after the call, from
+ * any slot (k_allele_counts, after the filters and before k_fmt_size, on the
+ * slot's stream; plain 64-bit atomics, so sums over batches, slots and
+ * devices are order-free).  min_base_quality < 0 is DCR_EARG.  The option
+ * changes no other output. */
+#define DCR_ALLELE_MAX_SITES (1 << 24)
+#define DCR_ALLELE_COLS 8
+int dcr_set_allele_sites(dcr_ctx *ctx, const int64_t *keys, int64_t n, int min_base_quality);
+/* The table so far into dst (host memory, uint64[n][DCR_ALLELE_COLS]): waits
+ * for every batch submitted so far on any slot, then copies.  The table is not
+ * reset and goes on accumulating.  DCR_EARG when no sites are set. */
+int dcr_allele_counts_fetch(dcr_ctx *ctx, uint64_t *dst);
+
 /* CPU restatement with the same contract (oracle/, test infrastructure):
    host pointers, single thread (or n_threads > 1) */
 int dcr_oracle_run(const dcr_params *params, const dcr_batch *in, dcr_out *ss, dcr_out *ds,

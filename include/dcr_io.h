@@ -286,6 +286,17 @@ int dcr_fmt_write_ss_filt(dcr_bgzw *w, const dcr_host_batch *hb, const dcr_fmt_o
 int dcr_fmt_mate_overlap(const dcr_host_batch *hb, const dcr_fmt_out *ds, int mode, int32_t n_fam,
                          int32_t *fam_ovl);
 
+/* The allele counts at given sites on the host (include/dcr.h
+ * dcr_set_allele_sites states the map, the calls and the table; the device's
+ * k_allele_counts gives the same words).  Adds the counts of processed
+ * families [0, n_fam), none of which fails, into table[n_keys][DCR_ALLELE_COLS]
+ * (the caller zeroes it), skipping the families fam_filt drops (low byte not
+ * 0; NULL: none).  keys as dcr_set_allele_sites takes them, n_keys > 0.  To be
+ * called after dcr_fmt_mate_overlap and dcr_fmt_filter: it counts the records
+ * as they are written.  Reads only. */
+int dcr_fmt_allele_counts(const dcr_host_batch *hb, const dcr_fmt_out *ds, const int64_t *keys, int64_t n_keys,
+                          int min_base_quality, int32_t n_fam, const int32_t *fam_filt, uint64_t *table);
+
 /* The consensus QC tables on the host (include/dcr.h dcr_metrics states the
  * definitions; the device's k_metrics gives the same words).  Adds the counts
  * of processed families [0, n_fam) into *m (the caller zeroes it), skipping
