@@ -58,6 +58,8 @@ EXPORTS = {
     "dcr_slot_overlap_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "dcr_set_allele_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
     "dcr_allele_counts_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "dcr_set_genome": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
+    "dcr_slot_genome_metrics_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     # include/dcr_inflate.h: BGZF inflate on the device
     "dcr_inflater_create": (ctypes.c_void_p, [ctypes.c_int]),
     "dcr_inflater_destroy": (None, [ctypes.c_void_p]),
@@ -138,6 +140,7 @@ class Context:
         self.base_metrics = False
         self.mate_overlap = 0
         self.allele_sites = 0            # sites of the table on the context (set_allele_sites), 0: off
+        self.genome = None               # the Genome on the context (set_genome), None: off
         if want_info:
             _check(lib.dcr_set_options(self._ctx, 1))
 
@@ -218,6 +221,23 @@ class Context:
         keys = np.ascontiguousarray(keys, np.int64)
         _check(load().dcr_set_allele_sites(self._ctx, keys.ctypes.data, n, int(min_base_quality)))
         self.allele_sites = n
+
+    def set_genome(self, genome):
+        """The device writer counts the errors against ``genome``
+        (params.Genome; include/dcr.h dcr_set_genome) for the batches it takes
+        from now on; None: off, the device copy freed.  The same object again
+        is no new upload."""
+        if genome is self.genome:
+            return
+        if genome is None:
+            _check(load().dcr_set_genome(self._ctx, None, None, 0))
+        else:
+            codes = np.ascontiguousarray(genome.codes, np.uint8)
+            off = np.ascontiguousarray(genome.ref_off, np.int64)
+            if not len(codes):
+                codes = np.zeros(1, np.uint8)       # every sequence absent: an address, never read
+            _check(load().dcr_set_genome(self._ctx, codes.ctypes.data, off.ctypes.data, len(off) - 1))
+        self.genome = genome
 
     def allele_counts(self):
         """The table so far, uint64 [sites, 8] (dcr_allele_counts_fetch: waits

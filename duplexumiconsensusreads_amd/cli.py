@@ -62,6 +62,17 @@ The records count as they are written, after ``--mate_overlap`` and every
 ``--filter_*``; ``--allele_min_base_quality Q`` makes a base below Q count as
 N.  Off by default; no other output byte changes with them.
 
+``--genome FILE.fa --genome_metrics_output FILE.json`` (not reference flags;
+each needs the other) count the consensus against a reference FASTA
+(include/dcr.h ``dcr_genome_metrics``): per level (the single-strand records,
+counted whether or not they are written, and the duplex records) the aligned
+bases, matches, mismatches, the substitution spectrum with and without its two
+neighbours, and the mismatches by cycle and by quality, of the consensus as
+called, before ``--mate_overlap`` and any ``--filter_*``.  The FASTA is plain
+text; only the sequences of the input header are kept, and their lengths must
+be the header's.  Off by default; no other output byte changes with them, and
+the summary gains one line.
+
 Batches are pipelined: a thread ingests batch k+1 while the device runs batch
 k and the main thread writes batch k-1.
 
@@ -184,7 +195,16 @@ def parse_args(argv):
     ap.add_argument("--allele_min_base_quality", required=False, default=0, metavar="Q",
                     type=params_mod.allele_min_base_quality,
                     help="for --allele_counts_output: a base below Q counts as N")
+    # not reference flags: errors against a reference FASTA (include/dcr.h dcr_genome_metrics)
+    ap.add_argument("--genome", required=False, default=None, type=str, metavar="FILE.fa",
+                    help="the genome the input was aligned to, plain-text FASTA; needs --genome_metrics_output")
+    ap.add_argument("--genome_metrics_output", required=False, default=None, type=str, metavar="FILE.json",
+                    help="count the single-strand and the duplex consensus reads as called against --genome: aligned "
+                         "bases, mismatches, the substitution spectrum, and the mismatches by cycle and quality into "
+                         "FILE.json")
     args = ap.parse_args(argv)
+    if (args.genome is None) != (args.genome_metrics_output is None):
+        raise ValueError("--genome and --genome_metrics_output need each other")
     if (args.allele_sites is None) != (args.allele_counts_output is None):
         raise ValueError("--allele_sites and --allele_counts_output need each other")
     return args
@@ -330,7 +350,7 @@ def gpu_inflate(device: int = 0):
 
 
 def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=False, base_tags=False,
-                base_metrics=False, mate_overlap=0, allele=None):
+                base_metrics=False, mate_overlap=0, allele=None, genome=None):
     """``ss_output``: this run also writes the single-strand records (a
     property of the run, set on the backend each time: the default backend
     is kept across runs).  ``flt``: this run's ConsensusFilter or None,
@@ -380,6 +400,11 @@ def _as_backend(backend, params, device=0, ss_output=False, flt=None, metrics=Fa
         be.set_allele_sites(*(allele or (None,)))
     elif allele:
         raise ValueError("this backend cannot count the alleles")
+    # --genome: the params.Genome or None; set each time too
+    if hasattr(be, "genome"):
+        be.genome = genome
+    elif genome is not None:
+        raise ValueError("this backend cannot count against a genome")
     return be
 
 
@@ -396,10 +421,10 @@ def _check_ss_output(args, say=True):
 
 
 def _check_metrics_output(args, say=True):
-    """--metrics_output and --base_metrics_output must name .json files; they
-    are created here, before the pass and before any output file, so a bad
-    path fails early."""
-    paths = [p for p in (args.metrics_output, args.base_metrics_output) if p is not None]
+    """--metrics_output, --base_metrics_output and --genome_metrics_output
+    must name .json files; they are created here, before the pass and before
+    any output file, so a bad path fails early."""
+    paths = [p for p in (args.metrics_output, args.base_metrics_output, args.genome_metrics_output) if p is not None]
     for path in paths:
         if not path.endswith(".json"):
             if say:
@@ -430,6 +455,28 @@ def _finish_metrics(path, total, done, to_json=None):
     else:
         with contextlib.suppress(OSError):
             os.remove(path)
+
+
+def _load_genome(args, header, stats=None):
+    """--genome: the FASTA reduced to the sequences of the input's ``header``
+    (params.load_genome; a compressed file, a wrong length or a name that
+    occurs twice is a ValueError, raised here before any output file exists).
+    Sets ``args.genome_data`` to the params.Genome, or None without the
+    option."""
+    args.genome_data = None
+    if args.genome is None:
+        return
+    if not args.genome_metrics_output.endswith(".json"):
+        return                              # _check_metrics_output reports it
+    args.genome_data = params_mod.load_genome(args.genome, params_mod.header_sequences(header))
+    if stats is not None:
+        stats["genome_load_s"] = args.genome_data.load_s
+
+
+def _genome_summary(c, total):
+    """The summary's counters of a block (``_print_summary``)."""
+    if total is not None:
+        c["genome_levels"] = params_mod.genome_totals(total)
 
 
 def _check_allele_output(args, header, say=True):
@@ -513,6 +560,9 @@ class _Driver:
         al = getattr(args, "allele", None)
         self.allele = None if al is None or len(al[0]) == 0 else (al[0], al[1])
         self.allele_total = None if al is None else np.zeros((len(al[0]), params_mod.ALLELE_COLS), np.uint64)
+        # --genome: the batches' blocks summed as the other tables'
+        self.genome = getattr(args, "genome_data", None)
+        self.genome_total = np.zeros(params_mod.GMET_WORDS, np.uint64) if self.genome is not None else None
 
     # -- stdout of one batch, in the reference's order --------------------------
     def _prints(self, hb, fail_f, kind, which, last_batch):
@@ -658,6 +708,8 @@ class _Driver:
                 self.metrics_total += res.metrics
             if self.base_metrics_total is not None:
                 self.base_metrics_total += res.base_metrics
+            if self.genome_total is not None:
+                self.genome_total += res.genome_metrics
         else:
             ss, ds, rstat = res
             fail_f, kind, which = native_io.first_failure(hb, ss, ds, F, rstat)
@@ -665,6 +717,9 @@ class _Driver:
             if self.metrics_total is not None:
                 # before the filter, which masks the duplex arrays in place
                 self.metrics_total += native_io.metrics(hb, ss, ds, fail_f)
+            if self.genome_total is not None:
+                # the consensus as called too: before the overlap step and the filter
+                self.genome_total += native_io.genome_metrics(hb, ss, ds, self.genome, fail_f)
             # after the tables (the consensus as called), before the filter (which sees what this leaves)
             ovl = native_io.apply_overlap(hb, ss, ds, self.overlap, fail_f) if self.overlap else None
             filt = native_io.apply_filter(hb, ss, ds, self.filter, fail_f) if self.filter is not None else None
@@ -863,6 +918,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
     _check_ss_output(args)
     ss_path = args.single_strand_output
     try:
+        _load_genome(args, ing.header, stats)       # before any file is created
         _check_allele_output(args, ing.header)
         try:
             _check_metrics_output(args)
@@ -874,11 +930,12 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
         raise
     met_path, met_total, done = args.metrics_output, None, False
     bmet_path, bmet_total = args.base_metrics_output, None
+    gmet_path, gmet_total = args.genome_metrics_output, None
     al_total = None
     try:
         be = _as_backend(backend, params, args.device, ss_path is not None, ConsensusFilter.from_args(args),
                          met_path is not None, args.per_base_tags, bmet_path is not None, args.mate_overlap,
-                         args.allele and args.allele[:2])
+                         args.allele and args.allele[:2], args.genome_data)
         cons, excl, unproc, *rest = _open_writers(
             [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
              "%s_filteredfamilies.bam" % consensus_filename[:-4]] + ([ss_path] if ss_path else []), ing.header, args,
@@ -886,6 +943,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
     except BaseException:
         _finish_metrics(met_path, None, False)      # no empty metrics file from a run that never started
         _finish_metrics(bmet_path, None, False)
+        _finish_metrics(gmet_path, None, False)
         _finish_allele(args, None, False)
         raise
     sscs = rest[0] if rest else None
@@ -893,7 +951,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
     t_open = time.perf_counter()
     try:
         drv = _Driver(args, params, be, ing, cons, excl, unproc, sscs)
-        met_total, bmet_total = drv.metrics_total, drv.base_metrics_total
+        met_total, bmet_total, gmet_total = drv.metrics_total, drv.base_metrics_total, drv.genome_total
         if stats is not None and "trace" in stats:
             drv.trace = stats["trace"]
         try:
@@ -910,6 +968,7 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
         c.update(drv.overlap_counts)
         al_total = drv.allele_total
         _allele_summary(c, al_total)
+        _genome_summary(c, gmet_total)
         if args.verbose:
             print("\n Input file has been completely read \n")
         _print_summary(c)
@@ -932,7 +991,10 @@ def main(argv: Optional[list] = None, backend=None, rng=random, stats: Optional[
                         try:
                             _finish_metrics(bmet_path, bmet_total, done, params_mod.base_metrics_json)
                         finally:
-                            _finish_allele(args, al_total, done)
+                            try:
+                                _finish_metrics(gmet_path, gmet_total, done, params_mod.genome_metrics_json)
+                            finally:
+                                _finish_allele(args, al_total, done)
         if stats is not None:
             stats["close_s"] = time.perf_counter() - t_close
             stats["close_writers_s"] = t_wclose - t_close
@@ -995,6 +1057,11 @@ def _print_summary(c):
         # only with --allele_sites: the families that were written, each once per site
         print("\n Allele counts at %d sites: %d sites covered, %d molecules counted, %d of them discordant."
               % (c["allele_sites"], c["allele_covered"], c["allele_molecules"], c["allele_discordant"]))
+    if "genome_levels" in c:
+        # only with --genome: the consensus as called, per level
+        print("\n Against the genome: " + "; ".join(
+            "%s consensus %d aligned bases, %d mismatches, %d per million" % ((name.replace("_", "-"),) + tuple(t))
+            for name, t in zip(params_mod.GMET_LEVELS, c["genome_levels"])) + ".")
 
 
 # -- sharded mode: one process per GPU over ranges of whole families ---------------
@@ -1100,7 +1167,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
                            ss_meta=len(parts) > 3)
     be = _as_backend(backend, params, device, len(parts) > 3, ConsensusFilter.from_args(args),
                      args.metrics_output is not None, args.per_base_tags, args.base_metrics_output is not None,
-                     args.mate_overlap, args.allele and args.allele[:2])
+                     args.mate_overlap, args.allele and args.allele[:2], args.genome_data)
     cons, excl, unproc, *rest = _open_writers(parts, header, args, ing)
     sscs = rest[0] if rest else None
     ing.set_rng_state(rng_state)
@@ -1123,6 +1190,7 @@ def _run_range(args, params, backend, path, rng, rng_state, rng_range, parts, de
         res["metrics"] = drv.metrics_total
         res["base_metrics"] = drv.base_metrics_total
         res["allele_counts"] = drv.allele_total
+        res["genome_metrics"] = drv.genome_total
         res["stats"] = dict(drv.stats)
         res["stdout"] = out.getvalue()
         try:
@@ -1420,6 +1488,7 @@ def _main_sharded(args, params, backend, rng, stats, group):
             print(OUTPUT_FORMAT_ERROR)
         raise ReferenceExit(1)
     _check_ss_output(args, say=rank == 0)
+    _load_genome(args, header, stats)       # every rank loads the FASTA itself
     _check_allele_output(args, header, say=rank == 0)   # every rank reads the sites: the ranks' tables line up
     _check_metrics_output(args, say=rank == 0)      # every rank: a bad path ends them all before any collective
     finals = [consensus_filename, "%s_filteredreads.bam" % consensus_filename[:-4],
@@ -1522,10 +1591,18 @@ def _main_sharded(args, params, backend, rng, stats, group):
                 if results[r].get("allele_counts") is not None:
                     al_total += results[r]["allele_counts"]
             _allele_summary(tot, al_total)
+        gmet = None
+        if args.genome_data is not None:
+            gmet = np.zeros(params_mod.GMET_WORDS, np.uint64)
+            for r in range(min(world, len(ranges))):
+                if results[r].get("genome_metrics") is not None:
+                    gmet += results[r]["genome_metrics"]
+            _genome_summary(tot, gmet)
         if args.verbose:
             print("\n Input file has been completely read \n")
         _print_summary(tot)
         _finish_allele(args, al_total, True)
+        _finish_metrics(args.genome_metrics_output, gmet, True, params_mod.genome_metrics_json)
         if args.metrics_output is not None:
             # integer sums: the ranks' totals add up to the single-process run's
             met = np.zeros(params_mod.MET_WORDS, np.uint64)
@@ -1542,6 +1619,7 @@ def _main_sharded(args, params, backend, rng, stats, group):
         return 0
     _finish_metrics(args.metrics_output, None, False)
     _finish_metrics(args.base_metrics_output, None, False)
+    _finish_metrics(args.genome_metrics_output, None, False)
     _finish_allele(args, None, False)
     st, ea = results[fail]["status"], results[fail]["exc_args"]
     if st == "exit":

@@ -226,6 +226,7 @@ struct WriterBufs {
     dcr::BaseMap bmap;
     dcr_base_metrics *base_metrics;   // k_base_metrics' accumulator; null unless base metrics are on (dcr_set_base_metrics)
     int32_t *fam_ovl;       // k_mate_overlap's counters [3F]; null unless a mode is set (dcr_set_mate_overlap)
+    dcr_genome_metrics *genome_metrics;   // k_genome_metrics' block; null unless a genome is set (dcr_set_genome)
 };
 
 // The second stream of dcr_submit_write_ss: the single-strand records'
@@ -270,10 +271,11 @@ void plan_writer_ss(int64_t F, Plan &p, WriterSsBufs &ws) {
 // k_base_filter's counts and with maps (the batch, when a base filter or the
 // per-base tags or the base metrics are on) the column maps, after every
 // other region (none without them); with bmet, k_base_metrics' accumulator
-// after those; with ovl (dcr_set_mate_overlap) k_mate_overlap's counters last
+// after those; with ovl (dcr_set_mate_overlap) k_mate_overlap's counters; with
+// gmet (dcr_set_genome) k_genome_metrics' block last
 void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd, Plan &p, WriterBufs &w,
                  WriterSsBufs *ws = nullptr, bool filt = false, bool met = false, const dcr_batch *maps = nullptr,
-                 bool bfilt = false, bool bmet = false, bool ovl = false) {
+                 bool bfilt = false, bool bmet = false, bool ovl = false, bool gmet = false) {
     w.names = p.take<char>((size_t)n_names + 1);
     w.fam_code = p.take<int64_t>((size_t)F);
     w.fam_rx = p.take<int64_t>(2 * (size_t)F);
@@ -304,6 +306,7 @@ void plan_writer(int64_t F, int64_t n_names, int64_t B, int64_t nbm, unsigned gd
     }
     w.base_metrics = bmet ? p.take<dcr_base_metrics>(1) : nullptr;
     w.fam_ovl = ovl ? p.take<int32_t>(3 * (size_t)F) : nullptr;
+    w.genome_metrics = gmet ? p.take<dcr_genome_metrics>(1) : nullptr;
 }
 }  // namespace
 
@@ -350,6 +353,7 @@ struct dcr_ctx {
         int32_t *h_fam_filt = nullptr;   // the caller's pinned fam_filt (dcr_slot_filter_out), or null
         dcr_metrics *h_metrics = nullptr;   // the caller's pinned counters (dcr_slot_metrics_out), or null
         dcr_base_metrics *h_base_metrics = nullptr;   // the same for dcr_slot_base_metrics_out
+        dcr_genome_metrics *h_genome_metrics = nullptr;   // the same for dcr_slot_genome_metrics_out
         int32_t *h_fam_ovl = nullptr;    // the caller's pinned fam_ovl (dcr_slot_overlap_out), or null
         bool busy = false;
     } slots[DCR_MAX_SLOTS];
@@ -372,6 +376,11 @@ struct dcr_ctx {
     unsigned long long *d_allele_tab = nullptr;
     int64_t n_allele = 0;
     int allele_min_q = 0;
+    // dcr_set_genome: one code a base for n_ref sequences back to back and their offsets [n_ref + 1],
+    // read by every slot's k_genome_metrics; all null / 0: off
+    uint8_t *d_genome = nullptr;
+    int64_t *d_ref_off = nullptr;
+    int32_t n_ref = 0;
     // the column maps of the batch being submitted (submit_write sets them around its
     // dcr_run_batch when a base filter, the per-base tags or the base metrics are on); all null otherwise
     dcr::BaseMap bmap{};
@@ -736,6 +745,8 @@ void dcr_destroy(dcr_ctx *c) {
     if (c->d_wtab) (void)hipFree(c->d_wtab);
     if (c->d_allele_keys) (void)hipFree(c->d_allele_keys);
     if (c->d_allele_tab) (void)hipFree(c->d_allele_tab);
+    if (c->d_genome) (void)hipFree(c->d_genome);
+    if (c->d_ref_off) (void)hipFree(c->d_ref_off);
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1092,13 +1103,16 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     const bool ovl = c->mate_overlap != 0;
     if (ovl && F && !S.h_fam_ovl)
         return fail(DCR_EARG, "a mate overlap mode is set but the slot has no fam_ovl destination (dcr_slot_overlap_out)");
+    const bool gmet = c->n_ref != 0;
+    if (gmet && !S.h_genome_metrics)
+        return fail(DCR_EARG, "a genome is set but the slot has no destination (dcr_slot_genome_metrics_out)");
     Plan wsz;
     plan_writer(F, m->n_names, B, nbm, gd, wsz, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt, bmet,
-                ovl);
+                ovl, gmet);
     if (wsz.off > S.wbuf.cap) HIP_TRY(S.wbuf.ensure(wsz.off + wsz.off / 8));
     Plan wp{(char *)S.wbuf.p};
     plan_writer(F, m->n_names, B, nbm, gd, wp, wb, ms ? &wsb : nullptr, filt, met, maps ? h : nullptr, bfilt, bmet,
-                ovl);
+                ovl, gmet);
     // H2D: inputs and writer metadata on the copy stream
     HIP_TRY(upload_inputs(h, db, c->s_h2d));
     if (m->n_names) HIP_TRY(hipMemcpyAsync(wb.names, m->names, (size_t)m->n_names, hipMemcpyHostToDevice, c->s_h2d));
@@ -1144,6 +1158,7 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     // the slot's counters start from zero for every batch (an empty batch gives zeros)
     if (met) HIP_TRY(hipMemsetAsync(wb.metrics, 0, sizeof(dcr_metrics), c->stream));
     if (bmet) HIP_TRY(hipMemsetAsync(wb.base_metrics, 0, sizeof(dcr_base_metrics), c->stream));
+    if (gmet) HIP_TRY(hipMemsetAsync(wb.genome_metrics, 0, sizeof(dcr_genome_metrics), c->stream));
     if (F) {
         hipLaunchKernelGGL(dcrw::k_famfail, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, c->stream, A);
         if (met) {
@@ -1183,6 +1198,35 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
                     1, std::min<int64_t>((2 * (f1 - f0) + wpg - 1) / wpg, (int64_t)c->n_cu));
                 hipLaunchKernelGGL(dcrw::k_base_metrics, dim3(gb), dim3(dcrw::kBmThreads), 0, c->stream, Ba);
                 f0 = f1;
+            }
+        }
+        if (gmet) {
+            // one wave per record, the single-strand level and then the duplex level, in k_base_metrics'
+            // place: before k_mate_overlap and the filters rewrite the duplex seq / qual.  At most one
+            // workgroup per CU (each ends with a global add per non-zero bin).  A launch's 32-bit LDS bins
+            // take at most one per base: the records are launched in ranges whose regions hold fewer
+            // than 2^32 columns, one range for every batch but an enormous one
+            const int wpg = dcrw::kGmThreads / 64;
+            const int64_t lim = (int64_t)1 << 32;
+            for (int lv = 0; lv < 2; ++lv) {
+                const int per = lv == 0 ? 4 : 2;
+                const int64_t *off = lv == 0 ? h->ss_col_off : h->ds_col_off;
+                const int64_t cols = lv == 0 ? h->ss_cols : h->ds_cols;
+                dcrw::GenomeMetricsArgs Ga{dout[lv], lv == 0 ? db.ss_col_off : db.ds_col_off, wb.fam_fail, wb.fam_tid,
+                                           c->d_genome, c->d_ref_off, c->n_ref, lv, 0, 0, wb.genome_metrics};
+                for (int64_t r0 = 0; r0 < per * F;) {
+                    int64_t r1 = per * F;
+                    if (cols >= lim) {
+                        // at least one record a launch: its len is an int32, below 2^32 whatever its region
+                        for (r1 = r0 + 1; r1 < per * F && off[r1 + 1] - off[r0] < lim; ++r1) {}
+                    }
+                    Ga.r0 = r0;
+                    Ga.r1 = r1;
+                    const unsigned gg = (unsigned)std::max<int64_t>(
+                        1, std::min<int64_t>((r1 - r0 + wpg - 1) / wpg, (int64_t)c->n_cu));
+                    hipLaunchKernelGGL(dcrw::k_genome_metrics, dim3(gg), dim3(dcrw::kGmThreads), 0, c->stream, Ga);
+                    r0 = r1;
+                }
             }
         }
         if (ovl) {
@@ -1305,6 +1349,9 @@ static int submit_write(dcr_ctx *c, int slot, const dcr_batch *h, const dcr_wmet
     if (met) HIP_TRY(hipMemcpyAsync(S.h_metrics, wb.metrics, sizeof(dcr_metrics), hipMemcpyDeviceToHost, c->s_d2h));
     if (bmet)
         HIP_TRY(hipMemcpyAsync(S.h_base_metrics, wb.base_metrics, sizeof(dcr_base_metrics), hipMemcpyDeviceToHost,
+                               c->s_d2h));
+    if (gmet)
+        HIP_TRY(hipMemcpyAsync(S.h_genome_metrics, wb.genome_metrics, sizeof(dcr_genome_metrics), hipMemcpyDeviceToHost,
                                c->s_d2h));
     HIP_TRY(hipMemcpyAsync(res->totals, wb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
     if (ms) HIP_TRY(hipMemcpyAsync(res_ss->totals, wsb.tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->s_d2h));
@@ -1436,6 +1483,60 @@ int dcr_allele_counts_fetch(dcr_ctx *c, uint64_t *dst) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(dst, c->d_allele_tab, (size_t)c->n_allele * DCR_ALLELE_COLS * sizeof(uint64_t),
                       hipMemcpyDeviceToHost));
+    return DCR_OK;
+}
+
+int dcr_set_genome(dcr_ctx *c, const uint8_t *codes, const int64_t *ref_off, int32_t n_ref) {
+    if (!c) return fail(DCR_EARG, "NULL context");
+    if (!codes || !ref_off || n_ref == 0) {
+        if (c->n_ref) {
+            // the genome may still be read: the batches in flight first
+            HIP_TRY(hipSetDevice(c->device));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            (void)hipFree(c->d_genome);
+            (void)hipFree(c->d_ref_off);
+        }
+        c->d_genome = nullptr;
+        c->d_ref_off = nullptr;
+        c->n_ref = 0;
+        return DCR_OK;
+    }
+    if (n_ref < 0) return fail(DCR_EARG, "genome: n_ref < 0");
+    if (ref_off[0] != 0) return fail(DCR_EARG, "genome: ref_off[0] must be 0");
+    for (int32_t t = 0; t < n_ref; ++t)
+        if (ref_off[t + 1] < ref_off[t]) return fail(DCR_EARG, "genome: ref_off must not decrease");
+    const int64_t total = ref_off[n_ref];
+    for (int64_t i = 0; i < total; ++i)
+        if (codes[i] > 4) return fail(DCR_EARG, "genome: a code above 4");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint8_t *dg = nullptr;
+    int64_t *dr = nullptr;
+    // never a zero-size allocation: a genome of absent sequences only still turns the counting on
+    hipError_t e = hipMalloc(&dg, (size_t)std::max<int64_t>(total, 16));
+    if (e == hipSuccess) e = hipMalloc(&dr, ((size_t)n_ref + 1) * sizeof(int64_t));
+    // a pageable source in chunks: the runtime stages each through its own pinned buffer
+    const int64_t chunk = (int64_t)64 << 20;
+    for (int64_t at = 0; e == hipSuccess && at < total; at += chunk)
+        e = hipMemcpy(dg + at, codes + at, (size_t)std::min(chunk, total - at), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dr, ref_off, ((size_t)n_ref + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (dg) (void)hipFree(dg);
+        if (dr) (void)hipFree(dr);
+        return fail(DCR_EHIP, hipGetErrorString(e));
+    }
+    if (c->d_genome) (void)hipFree(c->d_genome);
+    if (c->d_ref_off) (void)hipFree(c->d_ref_off);
+    c->d_genome = dg;
+    c->d_ref_off = dr;
+    c->n_ref = n_ref;
+    return DCR_OK;
+}
+
+int dcr_slot_genome_metrics_out(dcr_ctx *c, int slot, dcr_genome_metrics *pinned_dst) {
+    if (!c || slot < 0 || slot >= DCR_MAX_SLOTS) return fail(DCR_EARG, "bad argument");
+    if (c->slots[slot].busy) return fail(DCR_EARG, "slot still in flight (dcr_wait it first)");
+    c->slots[slot].h_genome_metrics = pinned_dst;
     return DCR_OK;
 }
 

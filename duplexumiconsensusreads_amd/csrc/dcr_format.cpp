@@ -866,4 +866,119 @@ int dcr_fmt_metrics(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_f
     return DCR_IO_OK;
 }
 
+// the tables of include/dcr.h (dcr_genome_metrics), as dcr_writer.hip's k_genome_metrics counts them;
+// here one record after the other, run by run, the genome's three codes sliding along an M run
+namespace {
+struct GmGenome {
+    const uint8_t *codes;
+    const int64_t *ref_off;
+    int32_t n_ref;
+    // the sequence of tid: its codes and length (absent or out of range: length 0)
+    const uint8_t *seq(int64_t tid, int64_t &len) const {
+        if (tid < 0 || tid >= n_ref) {
+            len = 0;
+            return codes;
+        }
+        len = ref_off[tid + 1] - ref_off[tid];
+        return codes + ref_off[tid];
+    }
+};
+inline int gm_at(const uint8_t *g, int64_t glen, int64_t p) {
+    if (p < 0 || p >= glen) return 4;
+    return g[p] < 4 ? g[p] : 4;
+}
+inline int gm_base(uint8_t c) {
+    switch (c | 0x20) {
+        case 'a': return 0; case 'c': return 1; case 'g': return 2; case 't': return 3;
+        default: return 4;
+    }
+}
+void gm_record(const GmGenome &G, int64_t tid, const dcr_fmt_out *o, int64_t ro, int64_t room, int32_t r, int lv,
+               int j, dcr_genome_metrics *m) {
+    auto clampi = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : v > hi ? hi : v; };
+    const int64_t len = clampi(o->len[r], room), ncig = clampi(o->n_cig[r], room);
+    const uint32_t *cig = o->cigar + ro;
+    const uint8_t *seq = o->seq + ro, *qual = o->qual + ro;
+    int64_t glen;
+    const uint8_t *g = G.seq(tid, glen);
+    uint64_t *n = m->n[lv];
+    n[0] += 1;
+    int64_t rp = o->pos[r], bi = 0;
+    for (int64_t k = 0; k < ncig && bi < len; ++k) {
+        const int64_t cnt = cig[k] >> 4;
+        const uint32_t op = cig[k] & 15u;
+        const int64_t here = std::min(cnt, len - bi);
+        if (op == 0u || op == 7u || op == 8u) {
+            int g5 = gm_at(g, glen, rp - 1), gc = gm_at(g, glen, rp);
+            for (int64_t t = 0; t < here; ++t) {
+                const int64_t i = bi + t;
+                const int g3 = gm_at(g, glen, rp + t + 1);
+                const int x = gm_base(seq[i]);
+                n[1] += 1;
+                if (gc == 4) {
+                    n[5] += 1;
+                } else if (x == 4) {
+                    n[4] += 1;
+                } else {
+                    const int mis = gc != x;
+                    n[2 + mis] += 1;
+                    m->sub[lv][j][gc][x] += 1;
+                    if (g5 < 4 && g3 < 4) m->tri[lv][j][g5][gc][g3][x] += 1;
+                    const int64_t ip = j == 0 ? i : len - 1 - i;
+                    const int64_t b = std::min<int64_t>(ip, DCR_GMET_CYC_BINS - 1);
+                    m->cyc[lv][j][0][b] += 1;
+                    m->qual[lv][0][qual[i]] += 1;
+                    if (mis) {
+                        m->cyc[lv][j][1][b] += 1;
+                        m->qual[lv][1][qual[i]] += 1;
+                    }
+                }
+                g5 = gc;
+                gc = g3;
+            }
+            rp += cnt;
+            bi += cnt;
+        } else if (op == 1u) {
+            n[6] += 1;
+            n[7] += (uint64_t)here;
+            bi += cnt;
+        } else if (op == 4u) {
+            bi += cnt;
+        } else if (op == 2u) {
+            n[8] += 1;
+            n[9] += (uint64_t)cnt;
+            rp += cnt;
+        } else if (op == 3u) {
+            rp += cnt;
+        }
+    }
+}
+}  // namespace
+
+int dcr_fmt_genome_metrics(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds,
+                           const uint8_t *codes, const int64_t *ref_off, int32_t n_ref, int32_t n_fam,
+                           const int32_t *fam_fail, dcr_genome_metrics *m) {
+    if (!hb || !ss || !ds || !codes || !ref_off || !m || n_ref <= 0 || n_fam < 0 || n_fam > hb->n_fam)
+        return fail(DCR_IO_EARG, "bad arguments");
+    if (!ss->pos || !ss->n_cig || !ss->cigar)
+        return fail(DCR_IO_EARG, "genome metrics: the single-strand results lack pos, n_cig or cigar");
+    if (ref_off[0] != 0) return fail(DCR_IO_EARG, "genome: ref_off[0] must be 0");
+    for (int32_t t = 0; t < n_ref; ++t)
+        if (ref_off[t + 1] < ref_off[t]) return fail(DCR_IO_EARG, "genome: ref_off must not decrease");
+    const GmGenome G{codes, ref_off, n_ref};
+    for (int32_t f = 0; f < n_fam; ++f) {
+        if (fam_fail && fam_fail[f] != 0) continue;
+        const int64_t tid = hb->fam_tid[f];
+        for (int k = 0; k < 4; ++k) {
+            const int32_t s = 4 * f + k;
+            gm_record(G, tid, ss, hb->ss_col_off[s], hb->ss_col_off[s + 1] - hb->ss_col_off[s], s, 0, k >> 1, m);
+        }
+        for (int j = 0; j < 2; ++j) {
+            const int32_t r = 2 * f + j;
+            gm_record(G, tid, ds, hb->ds_col_off[r], hb->ds_col_off[r + 1] - hb->ds_col_off[r], r, 1, j, m);
+        }
+    }
+    return DCR_IO_OK;
+}
+
 }  // extern "C"

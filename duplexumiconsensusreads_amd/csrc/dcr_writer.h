@@ -139,6 +139,22 @@ struct AlleleArgs {
     int32_t min_q;                  // a base below it calls N
 };
 
+// the errors against a genome (k_genome_metrics, dcr_set_genome): one level a launch, everything
+// read only but the slot's block
+struct GenomeMetricsArgs {
+    dcr_out o;                      // the level's device kernel outputs: ss (lv 0) or ds (lv 1), as called
+    const int64_t *col_off;         // the level's ss_col_off [4F+1] or ds_col_off [2F+1]
+    const int32_t *fam_fail;        // [F] from k_famfail
+    const int32_t *fam_tid;         // [F]
+    const uint8_t *codes;           // the context's genome, one code a base
+    const int64_t *ref_off;         // [n_ref + 1]
+    int32_t n_ref;
+    int32_t lv;                     // 0: four records a family, 1: two
+    int64_t r0, r1;                 // the records of this launch: their regions hold fewer than 2^32 columns
+    dcr_genome_metrics *out;        // the slot's block, zeroed before the first launch
+};
+constexpr int kGmThreads = 1024;    // k_genome_metrics' workgroup: 16 waves on one level's LDS tables
+
 struct DflArgs {
     const uint8_t *stream;
     const int64_t *stream_bytes;    // device scalar (rec_off[2F])
@@ -173,6 +189,7 @@ __global__ void k_fmt_write_ss_tags(FmtSsTagArgs T);
 __global__ void k_base_metrics(BaseMetricsArgs A);
 __global__ void k_mate_overlap(MateOverlapArgs A);
 __global__ void k_allele_counts(AlleleArgs A);
+__global__ void k_genome_metrics(GenomeMetricsArgs A);
 __global__ void k_deflate(DflArgs D);
 __global__ void k_compact(CompactArgs C);
 

@@ -9,6 +9,8 @@
 // (dcr_set_base_tags) kernels of their own format both streams, the default
 // ones staying as they are.  With the per-base QC tables on
 // (dcr_set_base_metrics) k_base_metrics counts over the same maps.
+// With a genome set (dcr_set_genome) k_genome_metrics counts the records as
+// called against it, at the end of this file.
 //
 // Reference (/root/reference/DuplexUMIConsensusReads.py): record fields
 // make_consensus_read :1352-1384, names / flags :892-968, duplex tags
@@ -2190,5 +2192,100 @@ __global__ __launch_bounds__(256) void k_allele_counts(AlleleArgs A) {
         ac_runs(A, R1, R0, true, base, s_lo, s_hi);
     }
 }
+
+// ---- the errors against a genome (dcr_set_genome; include/dcr.h states the
+// map, the codes and the tables).  One launch per level (A.lv: the four
+// single-strand records of a family, then its two duplex records), the same
+// kernel: one level's tables are 3,104 32-bit bins and twelve 64-bit words,
+// 12,512 bytes of LDS, so a workgroup does not wait for the LDS that both
+// levels together (25 KB) or k_base_metrics' 56 KB would.  Runs in
+// k_base_metrics' place: after the failure scan, before k_mate_overlap and the
+// filters rewrite the duplex seq / qual.  Reads only; writes the slot's block.
+//
+// The reduction is k_base_metrics': a wave per record, 64 bases of an M run a
+// step in a wave-uniform loop (the wave index comes from readfirstlane, so the
+// CIGAR walk and its branches are the whole wave's), n[] as popcounts of
+// ballots, the hot bin of sub and qual merged (bm_count), one LDS add per lane
+// for the cycle (64 consecutive bases are 64 bins) and tri, a whole step past
+// bin 511 summed over the wave; then one global 64-bit add per non-zero bin per
+// workgroup.  A base's position is the run's first position plus the lane: the
+// genome bytes of a step are 64 consecutive bytes (and their two neighbours).
+// No 32-bit bin wraps: a base adds at most 1 to a bin and a launch covers
+// records [r0, r1) whose regions hold fewer than 2^32 columns (the host splits
+// a larger batch).  Every index is clamped to its region (mo_rec, gm_at).
+#define GM_FN __device__ __forceinline__
+GM_FN int gm_lane() { return lane_id(); }
+GM_FN unsigned long long gm_pop(bool p) { return bm_pop(p); }
+GM_FN unsigned long long gm_once(unsigned long long v) { return v; }
+GM_FN void gm_count(uint32_t *h, int bin, bool act) { bm_count(h, bin, act); }
+GM_FN void gm_wave_add(uint32_t *p, bool pred) {
+    const uint32_t c = (uint32_t)bm_pop(pred);
+    if (c && lane_id() == 0) atomicAdd(p, c);
+}
+GM_FN void gm_add(uint32_t *p) { atomicAdd(p, 1u); }
+GM_FN int gm_code(uint8_t c) { return bm_code(c); }
+#include "dcr_genome_body.h"
+
+constexpr int kGmWords = 12 + kGmBins;      // one level's words in the block
+static_assert(sizeof(dcr_genome_metrics) == 8 * 2 * (size_t)kGmWords &&
+                  offsetof(dcr_genome_metrics, sub) == 8 * 24 &&
+                  offsetof(dcr_genome_metrics, tri) == 8 * (24 + 2 * (kGmTri - kGmSub)) &&
+                  offsetof(dcr_genome_metrics, cyc) == 8 * (24 + 2 * (kGmCyc - kGmSub)) &&
+                  offsetof(dcr_genome_metrics, qual) == 8 * (24 + 2 * (kGmQual - kGmSub)),
+              "k_genome_metrics' LDS layout follows dcr_genome_metrics");
+
+struct GmShared {
+    unsigned long long n[12];
+    uint32_t cnt[kGmBins];
+};
+
+__global__ __launch_bounds__(kGmThreads) void k_genome_metrics(GenomeMetricsArgs A) {
+    __shared__ GmShared S;
+    for (int i = threadIdx.x; i < (int)(sizeof(GmShared) / 4); i += kGmThreads) reinterpret_cast<uint32_t *>(&S)[i] = 0;
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * kGmThreads + threadIdx.x) / kW));
+    const int nw = (int)(gridDim.x * (kGmThreads / kW));
+    const int per = A.lv == 0 ? 2 : 1;          // log2 of a family's records on this level
+    unsigned long long n[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t r = A.r0 + wave; r < A.r1; r += nw) {
+        const int64_t f = r >> per;
+        if (A.fam_fail[f] != 0) continue;
+        MoRec M;
+        mo_rec(A.o, A.col_off, r, M);
+        const GmRec R{M.cig, M.seq, M.qual, M.len, M.ncig, M.pos};
+        const int64_t tid = A.fam_tid[f];
+        const uint8_t *g = A.codes;
+        int64_t glen = 0;
+        if (tid >= 0 && tid < (int64_t)A.n_ref) {
+            const int64_t o = A.ref_off[tid];
+            glen = A.ref_off[tid + 1] - o;
+            g += o;
+        }
+        gm_record(R, (int)((r >> (per - 1)) & 1), g, glen, n, S.cnt);
+    }
+    if (lane_id() == 0)
+        for (int t = 0; t < 12; ++t)
+            if (n[t]) atomicAdd(&S.n[t], n[t]);
+    __syncthreads();
+    // the workgroup's tables into the slot's: one 64-bit add per non-zero bin.  Word w of the level
+    // lies in its table of the block after the tables' parts of the levels before it
+    unsigned long long *out = reinterpret_cast<unsigned long long *>(A.out);
+    for (int w = threadIdx.x; w < kGmWords; w += kGmThreads) {
+        unsigned long long v;
+        int at;
+        if (w < 12) {
+            v = S.n[w];
+            at = A.lv * 12 + w;
+        } else {
+            const int b = w - 12;
+            v = S.cnt[b];
+            const int t0 = b < kGmTri ? kGmSub : b < kGmCyc ? kGmTri : b < kGmQual ? kGmCyc : kGmQual;
+            const int t1 = b < kGmTri ? kGmTri : b < kGmCyc ? kGmCyc : b < kGmQual ? kGmQual : kGmBins;
+            at = 24 + 2 * t0 + A.lv * (t1 - t0) + (b - t0);
+        }
+        if (v) atomicAdd(&out[at], v);
+    }
+}
+#undef GM_FN
 
 }  // namespace dcrw

@@ -107,6 +107,7 @@ def load():
             "dcr_fmt_metrics": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
             "dcr_fmt_mate_overlap": (_i32, [_vp, _vp, _i32, _i32, _vp]),
             "dcr_fmt_allele_counts": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _i32, _i32, _vp, _vp]),
+            "dcr_fmt_genome_metrics": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
             "dcr_fmt_write_filt": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
             "dcr_fmt_write_ss_filt": (_i32, [_vp, _vp, _vp, _i32, _vp]),
             "dcr_synth_write": (_i32, [_vp, _vp, _i32]),
@@ -496,6 +497,29 @@ def metrics(hb: HostBatch, ss: FmtOut, ds: FmtOut, n_fam: int, fam_fail=None) ->
     if load().dcr_fmt_metrics(ctypes.byref(hb.s), ctypes.byref(ss), ctypes.byref(ds), n_fam,
                               ff.ctypes.data if ff is not None else None, out.ctypes.data) != 0:
         raise _err("consensus metrics")
+    return out
+
+
+def genome_metrics(hb: HostBatch, ss: FmtOut, ds: FmtOut, genome, n_fam: int, fam_fail=None) -> np.ndarray:
+    """dcr_fmt_genome_metrics: the errors against ``genome`` (params.Genome;
+    include/dcr.h dcr_genome_metrics) of the single-strand and duplex records
+    of processed families [0, n_fam) as a uint64 block
+    (params.genome_metrics_fields names its tables); with ``fam_fail`` (int32
+    per family) the families whose word is not 0 are skipped.  ``ss`` needs
+    pos, n_cig and cigar.  To be called before ``apply_overlap`` and
+    ``apply_filter``, which rewrite the duplex arrays in place."""
+    from .params import GMET_WORDS
+    out = np.zeros(GMET_WORDS, np.uint64)
+    ff = None if fam_fail is None else np.ascontiguousarray(fam_fail, np.int32)
+    codes = np.ascontiguousarray(genome.codes, np.uint8)
+    off = np.ascontiguousarray(genome.ref_off, np.int64)
+    if not len(codes):
+        codes = np.zeros(1, np.uint8)   # every sequence absent: an address, never read
+    if load().dcr_fmt_genome_metrics(ctypes.byref(hb.s), ctypes.byref(ss), ctypes.byref(ds), codes.ctypes.data,
+                                     off.ctypes.data,
+                                     len(off) - 1, n_fam, ff.ctypes.data if ff is not None else None,
+                                     out.ctypes.data) != 0:
+        raise _err("genome metrics")
     return out
 
 

@@ -488,6 +488,172 @@ def allele_totals(table):
     return len(table), int((depth > 0).sum()), int(depth.sum()), int(table[:, 6].sum())
 
 
+# ---- errors against a genome (include/dcr.h dcr_genome_metrics; --genome, --genome_metrics_output) ----
+GMET_CYC_BINS, GMET_QUAL_BINS = 512, 256
+
+
+class DcrGenomeMetrics(ctypes.Structure):
+    """Mirror of ``dcr_genome_metrics`` (include/dcr.h): every field uint64."""
+    _fields_ = [("n", ctypes.c_uint64 * 12 * 2),
+                ("sub", ctypes.c_uint64 * 4 * 4 * 2 * 2),
+                ("tri", ctypes.c_uint64 * 4 * 4 * 4 * 4 * 2 * 2),
+                ("cyc", ctypes.c_uint64 * GMET_CYC_BINS * 2 * 2 * 2),
+                ("qual", ctypes.c_uint64 * GMET_QUAL_BINS * 2 * 2)]
+
+
+GMET_WORDS = ctypes.sizeof(DcrGenomeMetrics) // 8       # 6,232
+GMET_LEVELS = ("single_strand", "duplex")
+GMET_N_NAMES = ("records", "aligned_bases", "matches", "mismatches", "no_calls", "genome_unknown", "insertions",
+                "inserted_bases", "deletions", "deleted_positions")
+
+
+def genome_metrics_fields(words):
+    """The tables of a ``uint64[GMET_WORDS]`` block as a dict of array views,
+    shaped as the struct's fields."""
+    words = np.asarray(words).reshape(-1)
+    if len(words) != GMET_WORDS:
+        raise ValueError("not a dcr_genome_metrics block")
+    out = {}
+    for name, ct in DcrGenomeMetrics._fields_:
+        f = getattr(DcrGenomeMetrics, name)
+        shape, t = [], ct
+        while hasattr(t, "_length_"):
+            shape.append(t._length_)
+            t = t._type_
+        out[name] = words[f.offset // 8:(f.offset + f.size) // 8].reshape(shape)
+    return out
+
+
+def genome_metrics_json(words) -> str:
+    """The ``--genome_metrics_output`` file of a counter block: named keys,
+    integers only, sorted keys and fixed separators, so the same counters
+    always give the same bytes."""
+    import json
+    m = genome_metrics_fields(words)
+    doc = {"version": 1, "bins": {"cycle_max": GMET_CYC_BINS - 1}, "codes": "ACGT"}
+    for lv, level in enumerate(GMET_LEVELS):
+        d = {name: int(m["n"][lv, i]) for i, name in enumerate(GMET_N_NAMES)}
+        d["sub"], d["tri"], d["cycle"] = {}, {}, {}
+        for j, read in enumerate(("read1", "read2")):
+            d["sub"][read] = [[int(v) for v in row] for row in m["sub"][lv, j]]
+            t = m["tri"][lv, j]
+            d["tri"][read] = [[int(a), int(b), int(c), int(x), int(t[a, b, c, x])] for a, b, c, x in zip(*np.nonzero(t))]
+            n = len(_trimmed(m["cyc"][lv, j, 0]))
+            d["cycle"][read] = {"compared": [int(v) for v in m["cyc"][lv, j, 0, :n]],
+                                "mismatches": [int(v) for v in m["cyc"][lv, j, 1, :n]]}
+        n = len(_trimmed(m["qual"][lv, 0]))
+        d["qual"] = {"compared": [int(v) for v in m["qual"][lv, 0, :n]],
+                     "mismatches": [int(v) for v in m["qual"][lv, 1, :n]]}
+        doc[level] = d
+    return json.dumps(doc, sort_keys=True, separators=(",", ":")) + "\n"
+
+
+def genome_totals(words):
+    """Per level (aligned bases, mismatches, mismatches per million compared
+    bases, an integer quotient): the summary's line."""
+    n = genome_metrics_fields(words)["n"]
+    out = []
+    for lv in range(2):
+        cmp_, mis = int(n[lv, 2]) + int(n[lv, 3]), int(n[lv, 3])
+        out.append((int(n[lv, 1]), mis, mis * 1000000 // cmp_ if cmp_ else 0))
+    return out
+
+
+def header_sequences(header: bytes):
+    """(name, length) of the references of a BAM header as stored."""
+    names = header_references(header)
+    (l_text,) = struct.unpack_from("<i", header, 4)
+    p = 8 + l_text + 4
+    out = []
+    for name in names:
+        (ln,) = struct.unpack_from("<i", header, p)
+        (length,) = struct.unpack_from("<i", header, p + 4 + ln)
+        out.append((name, length))
+        p += 4 + ln + 4
+    return out
+
+
+_GENOME_LUT = np.full(256, 4, np.uint8)
+for _i, _c in enumerate("ACGT"):
+    _GENOME_LUT[ord(_c)] = _GENOME_LUT[ord(_c.lower())] = _i
+for _c in b"\n\r":
+    _GENOME_LUT[_c] = 255               # line ends: no base
+del _i, _c
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class Genome:
+    """A genome as dcr_set_genome takes it: ``codes`` uint8, one per base (A C
+    G T 0..3, anything else 4), the sequences of ``names`` back to back;
+    ``ref_off`` int64 [len(names) + 1]; a sequence the FASTA lacks has length
+    0.  ``load_s``: what the loading took."""
+    codes: np.ndarray
+    ref_off: np.ndarray
+    names: tuple
+    load_s: float = 0.0
+
+
+def load_genome(path, sequences) -> Genome:
+    """The FASTA ``path`` (plain text; ``.gz`` / ``.bgz`` or gzip bytes are a
+    ValueError) reduced to the ``sequences`` [(name, length)] of the input
+    header, in that order.  A sequence's name is the text after '>' up to the
+    first whitespace; upper and lower case fold together; the lines may have
+    any lengths, end in LF or CRLF, and the last needs no line end.  Sequences
+    the header does not name are skipped; one of the header that the file lacks
+    is absent (length 0).  A sequence whose length differs from the header's,
+    and a name that occurs twice in the file, are ValueErrors naming it.  A
+    ``.fai`` beside the file is not needed and not read.  The bytes go through
+    one lookup table and one mask per kept sequence (numpy), never a loop per
+    line."""
+    import time
+    t0 = time.perf_counter()
+    if path.endswith((".gz", ".bgz")):
+        raise ValueError("--genome %s: a compressed FASTA is not supported, give the plain text" % path)
+    data = np.fromfile(path, np.uint8)
+    if len(data) >= 2 and data[0] == 0x1f and data[1] == 0x8b:
+        raise ValueError("--genome %s: a compressed FASTA is not supported, give the plain text" % path)
+    if not sequences:
+        raise ValueError("--genome: the input header names no sequence")
+    want = {}
+    for t, (name, _) in enumerate(sequences):
+        want.setdefault(name, t)
+    # the header lines: '>' at the start of the file or after a line end
+    gt = np.flatnonzero(data == ord(">"))
+    gt = gt[(gt == 0) | (data[np.maximum(gt, 1) - 1] == 10)]
+    if len(data) and (len(gt) == 0 or gt[0] != 0) and np.any(_GENOME_LUT[data[:int(gt[0]) if len(gt) else None]] != 255):
+        raise ValueError("--genome %s: text before the first '>' line" % path)
+    ends = np.append(gt[1:], len(data))
+    seen, spans = set(), {}
+    for start, end in zip(gt.tolist(), ends.tolist()):         # one step per sequence
+        width = 256
+        while True:
+            line = data[start:min(start + width, end)]
+            nl = np.flatnonzero(line == 10)
+            if len(nl) or start + width >= end:
+                break
+            width *= 16
+        body = start + (int(nl[0]) + 1 if len(nl) else len(line))
+        text = line[1:int(nl[0]) if len(nl) else len(line)].tobytes().decode("latin-1").split()
+        name = text[0] if text else ""
+        if name in seen:
+            raise ValueError("--genome %s: the sequence %r occurs twice" % (path, name))
+        seen.add(name)
+        if name in want:
+            spans[want[name]] = (body, end)
+    lengths = [ln if t in spans else 0 for t, (_, ln) in enumerate(sequences)]
+    ref_off = np.zeros(len(sequences) + 1, np.int64)
+    np.cumsum(lengths, out=ref_off[1:])
+    codes = np.empty(int(ref_off[-1]), np.uint8)
+    for t, (body, end) in sorted(spans.items()):
+        seq = _GENOME_LUT[data[body:end]]
+        seq = seq[seq != 255]
+        if len(seq) != lengths[t]:
+            raise ValueError("--genome %s: the sequence %r has %d bases, the input header says %d"
+                             % (path, sequences[t][0], len(seq), lengths[t]))
+        codes[int(ref_off[t]):int(ref_off[t + 1])] = seq
+    return Genome(codes, ref_off, tuple(name for name, _ in sequences), time.perf_counter() - t0)
+
+
 @dataclasses.dataclass(frozen=True)
 class ConsensusFilter:
     """The ``--filter_*`` options, parsed; None = that rule is off."""

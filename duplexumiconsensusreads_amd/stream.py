@@ -134,8 +134,9 @@ class _WriterOut:
         self.met = None                  # pinned dcr_metrics, made when metrics are first on
         self.bmet = None                 # pinned dcr_base_metrics, made when base metrics are first on
         self.ovl = None                  # pinned fam_ovl, made when --mate_overlap is first set
+        self.gmet = None                 # pinned dcr_genome_metrics, made when a genome is first set
 
-    def ensure(self, n_fam, bgzf_bytes, filt=False, met=False, bmet=False, ovl=False):
+    def ensure(self, n_fam, bgzf_bytes, filt=False, met=False, bmet=False, ovl=False, gmet=False):
         if n_fam > self.cap_f or self.small is None:
             self.cap_f = int(n_fam * 1.25) + 64
             self.small = Pinned(self.lib, 12 * self.cap_f + 64)
@@ -159,6 +160,10 @@ class _WriterOut:
             from .params import BMET_WORDS
             self.bmet = Pinned(self.lib, 8 * BMET_WORDS)
             self.base_metrics = self.bmet.array[:8 * BMET_WORDS].view(np.uint64)
+        if gmet and self.gmet is None:
+            from .params import GMET_WORDS
+            self.gmet = Pinned(self.lib, 8 * GMET_WORDS)
+            self.genome_metrics = self.gmet.array[:8 * GMET_WORDS].view(np.uint64)
         if bgzf_bytes > self.cap_b:
             self.cap_b = int(bgzf_bytes * 1.25) + (1 << 20)
             self.blocks = Pinned(self.lib, self.cap_b)
@@ -182,16 +187,19 @@ class WriterResult:
     block, overwritten when the slot is submitted again); None without.  With
     ``base_metrics`` on, ``base_metrics``: the batch's dcr_base_metrics in the
     same way; None without.  With ``mate_overlap`` set, ``fam_ovl``: compared,
-    disagree, changed per family (int32 [3 * n_fam]); None without."""
+    disagree, changed per family (int32 [3 * n_fam]); None without.  With a
+    genome set, ``genome_metrics``: the batch's dcr_genome_metrics as the other
+    blocks; None without."""
 
     def __init__(self, stream, slot, out, n_fam, out_ss=None, filtered=False, metrics=False, base_metrics=False,
-                 overlap=False):
+                 overlap=False, genome=False):
         self._stream, self._slot = stream, slot
         self.fam_fail = out.fam_fail[:n_fam]
         self.fam_filt = out.fam_filt[:n_fam] if filtered else None
         self.metrics = out.metrics if metrics else None
         self.base_metrics = out.base_metrics if base_metrics else None
         self.fam_ovl = out.fam_ovl[:3 * n_fam] if overlap else None
+        self.genome_metrics = out.genome_metrics if genome else None
         self.ds_len = out.ds_len[:2 * n_fam]
         self.bgzf_bytes, self.record_bytes, self.blocks = (int(x) for x in out.totals[:3])
         self.bgzf = out.blocks.array[:self.bgzf_bytes]
@@ -257,7 +265,14 @@ class DeviceStream:
     ``set_allele_sites`` (called per run too, --allele_sites): the device
     writer counts the alleles at the sites into a table on the context
     (dcr_set_allele_sites), which ``allele_counts`` fetches; on the host path
-    the caller counts (native_io.allele_counts)."""
+    the caller counts (native_io.allele_counts).
+
+    ``genome`` (set per run too, --genome): a params.Genome or None.  The
+    device writer uploads it once (dcr_set_genome, with the first batch), counts
+    the errors against it and ``result`` carries them as ``genome_metrics``; on
+    the host path the caller counts (native_io.genome_metrics), and the
+    single-strand pos, n_cig and cigar are downloaded for it.  None frees the
+    device copy with the next batch or ``close``."""
 
     def __init__(self, ctx, n_slots=2, owns_ctx=False, device_writer=True, persistent=False):
         """``persistent``: ``close`` only drains the slots (the context and the
@@ -277,6 +292,7 @@ class DeviceStream:
         self.base_metrics = False
         self.mate_overlap = 0
         self.allele = None               # (keys, min base quality) of set_allele_sites, or None
+        self.genome = None
         self.wouts_ss = None
         self.lib = _lib.load()
         self.n_slots = n_slots
@@ -325,13 +341,17 @@ class DeviceStream:
             counted = bool(self.metrics)
             based = bool(self.base_metrics)
             ovl = int(self.mate_overlap or 0)
-            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered, counted, based, ovl != 0)
+            gen = self.genome is not None
+            wo.ensure(s.n_fam, max(64 << 20, 2 * s.n_bases // 3), filtered, counted, based, ovl != 0, gen)
             # the context may serve other streams: its filter, metrics and tags are this stream's for this batch
             self.ctx.set_filter(self.filter)
             self.ctx.set_metrics(counted)
             self.ctx.set_base_tags(self.base_tags)
             self.ctx.set_base_metrics(based)
             self.ctx.set_mate_overlap(ovl)
+            self.ctx.set_genome(self.genome)
+            if gen:
+                _lib._check(self.lib.dcr_slot_genome_metrics_out(self.ctx._ctx, slot, wo.gmet.ptr))
             if ovl:
                 _lib._check(self.lib.dcr_slot_overlap_out(self.ctx._ctx, slot, wo.ovl.ptr))
             if based:
@@ -359,14 +379,14 @@ class DeviceStream:
                                                          ctypes.byref(ms), ctypes.byref(self._wres),
                                                          ctypes.byref(self._wres_ss)))
                 self.busy[slot] = True
-                return (slot, s.n_fam, True, filtered, counted, based, ovl != 0)
+                return (slot, s.n_fam, True, filtered, counted, based, ovl != 0, gen)
             _lib._check(self.lib.dcr_submit_write(self.ctx._ctx, slot, ctypes.byref(self._b), ctypes.byref(m),
                                                   ctypes.byref(self._wres)))
             self.busy[slot] = True
-            return (slot, s.n_fam, False, filtered, counted, based, ovl != 0)
+            return (slot, s.n_fam, False, filtered, counted, based, ovl != 0, gen)
         out = self.outs[slot]
         out.ensure(4 * s.n_fam, s.ss_cols, 2 * s.n_fam, s.ds_cols, s.n_reads,
-                   SS_FIELDS_FULL if self.ss_output else SS_FIELDS)
+                   SS_FIELDS_FULL if self.ss_output or self.genome is not None else SS_FIELDS)
         self._b = hb.batch_struct()
         so, do = out.dcr_out("ss"), out.dcr_out("ds")
         from . import _lib
@@ -398,7 +418,7 @@ class DeviceStream:
                     grown = True
             if not grown:
                 _lib._check(rc)
-            return WriterResult(self, slot, wo, n_fam, ws, handle[3], handle[4], handle[5], handle[6])
+            return WriterResult(self, slot, wo, n_fam, ws, handle[3], handle[4], handle[5], handle[6], handle[7])
         slot = handle
         _lib._check(self.lib.dcr_wait(self.ctx._ctx, slot))
         self.busy[slot] = False
@@ -415,6 +435,9 @@ class DeviceStream:
                 else:
                     self.lib.dcr_wait(self.ctx._ctx, slot)
                 self.busy[slot] = False
+        if self.device_writer and self.ctx.genome is not None:
+            self.genome = None
+            self.ctx.set_genome(None)    # set per run: a kept backend does not keep the genome
         if self.persistent and not final:
             return
         self.closed = True
@@ -426,7 +449,7 @@ class DeviceStream:
             if o.mem is not None:
                 o.mem.free()
         for w in self.wouts + (self.wouts_ss or []):
-            for m in (w.small, w.blocks, w.filt, w.met, w.bmet, w.ovl):
+            for m in (w.small, w.blocks, w.filt, w.met, w.bmet, w.ovl, w.gmet):
                 if m is not None:
                     m.free()
         if self.owns_ctx:
@@ -443,6 +466,7 @@ class CallBackend:
         self.metrics = False             # counted by the caller (native_io.metrics)
         self.mate_overlap = 0            # applied by the caller (native_io.apply_overlap)
         self.allele = None               # counted by the caller (native_io.allele_counts)
+        self.genome = None               # counted by the caller (native_io.genome_metrics)
         self._res = {}
         self._k = 0
 

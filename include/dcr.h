@@ -608,6 +608,84 @@ int dcr_set_allele_sites(dcr_ctx *ctx, const int64_t *keys, int64_t n, int min_b
  * reset and goes on accumulating.  DCR_EARG when no sites are set. */
 int dcr_allele_counts_fetch(dcr_ctx *ctx, uint64_t *dst);
 
+/* Errors against a genome (not a reference-script feature; "genome" is the
+ * reference FASTA, because "reference" means the reference script here.  What a
+ * mismatch counter run over the written files would count: the rules below are
+ * the specification, no other tool was run).  With a genome set,
+ * dcr_submit_write[_ss] compares every aligned base of the consensus records as
+ * called with the genome's base on its position and counts.
+ *
+ * Which records count, over the families f of the batch with fam_fail[f] == 0:
+ *   lv 0   the four single-strand records s = 4f + k, whether or not the
+ *          single-strand stream is written; their read index is j = k >> 1
+ *   lv 1   the two duplex records r = 2f + j
+ * as called: before k_mate_overlap and before every filter, beside
+ * k_base_metrics.
+ *
+ * The map of a record is the one of dcr_set_mate_overlap above (pos, CIGAR with
+ * SAM semantics in 64-bit arithmetic, len and n_cig clamped to the record's
+ * region; the walk ends at the last operation or once the base index has
+ * reached len).  An M / = / X run of n gives min(n, len - base index) bases
+ * with a position.  Of an I run the run counts once and min(n, len - base
+ * index) bases; of a D run the run counts once and n positions.  S, N, H, P
+ * and the unused codes count nothing.  An operation at or past len is not
+ * reached and counts nothing.
+ *
+ * The genome: codes[] holds one byte per base, A C G T as 0 1 2 3 and anything
+ * else 4, for n_ref sequences back to back; sequence t is
+ * codes[ref_off[t] .. ref_off[t + 1]), of length 0 when the FASTA lacks it.
+ *   code(t, p) = codes[ref_off[t] + p] when 0 <= t < n_ref and
+ *                0 <= p < ref_off[t + 1] - ref_off[t]; otherwise 4
+ * For base i of a record of family f on position p, with t = fam_tid[f]:
+ *   g = code(t, p), g5 = code(t, p - 1), g3 = code(t, p + 1)
+ *   x = the base's code: A a 0, C c 1, G g 2, T t 3, anything else 4 (the
+ *       code of dcr_base_metrics.pair)
+ *   q = the record's quality byte of the base
+ *   i' = i for j = 0 and len - 1 - i for j = 1 (dcr_base_metrics.cyc's cycle
+ *       from the sequencing 5' end), len the clamped one
+ * Tables:
+ *   n[lv][0]  records            [1] bases with a position
+ *        [2]  of those g < 4 && x < 4 && g == x       [3] g < 4 && x < 4 && g != x
+ *        [4]  g < 4 && x == 4    [5] g == 4 (past either end of the sequence,
+ *             an absent sequence and a tid outside [0, n_ref) included)
+ *        [6]  I runs   [7] I bases   [8] D runs   [9] D positions   [10] [11] 0
+ *        so [1] == [2] + [3] + [4] + [5]
+ *   sub[lv][j][g][x]        the bases with g < 4 && x < 4, in the genome's
+ *        orientation (as SEQ is stored), the diagonal included; split by j so
+ *        that the reverse read can be folded by complementing
+ *   tri[lv][j][g5][g][g3][x]   where sub counts and g5 < 4 && g3 < 4 (so never
+ *        at the first or the last position of a sequence)
+ *   cyc[lv][j][what][min(i', 511)]   what 0: where sub counts; 1: of those g != x
+ *   qual[lv][what][q]       what as in cyc
+ * Every table is an integer sum: totals over batches or devices are sums of
+ * the blocks in any order.  Mismatches at true variants are in the counts. */
+#define DCR_GMET_CYC_BINS 512
+#define DCR_GMET_QUAL_BINS 256
+typedef struct dcr_genome_metrics {
+    uint64_t n[2][12];
+    uint64_t sub[2][2][4][4];
+    uint64_t tri[2][2][4][4][4][4];
+    uint64_t cyc[2][2][2][DCR_GMET_CYC_BINS];
+    uint64_t qual[2][2][DCR_GMET_QUAL_BINS];
+} dcr_genome_metrics;   /* 6,232 words, 49,856 bytes */
+/* The genome onto the device.  codes / ref_off are host memory (pageable is
+ * fine; copied in chunks), ref_off[0] == 0, non-decreasing, n_ref + 1 entries,
+ * every code <= 4; anything else is DCR_EARG and leaves the state as it was.
+ * Waits for the batches in flight, then uploads into device memory that lives
+ * on the context and turns the counting on for the batches submitted afterwards
+ * (k_genome_metrics, once per level, after k_base_metrics' place and before
+ * k_mate_overlap, on the slot's stream).  n_ref == 0 or a NULL pointer frees the
+ * memory and turns the counting off: the default, in which nothing is
+ * allocated, uploaded, launched, copied or zeroed and no output byte changes.
+ * With the counting on no output byte changes either. */
+int dcr_set_genome(dcr_ctx *ctx, const uint8_t *codes, const int64_t *ref_off, int32_t n_ref);
+/* Where a slot's block goes (pinned host memory, one dcr_genome_metrics,
+ * written whole for every batch submitted on the slot while a genome is set:
+ * the batch's own counts, not a running total): copied with fam_fail, on the
+ * same stream and before the same event, so it is complete when
+ * dcr_wait_write[_ss] returns.  NULL removes it. */
+int dcr_slot_genome_metrics_out(dcr_ctx *ctx, int slot, dcr_genome_metrics *pinned_dst);
+
 /* CPU restatement with the same contract (oracle/, test infrastructure):
    host pointers, single thread (or n_threads > 1) */
 int dcr_oracle_run(const dcr_params *params, const dcr_batch *in, dcr_out *ss, dcr_out *ds,

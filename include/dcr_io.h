@@ -306,6 +306,21 @@ struct dcr_metrics;
 int dcr_fmt_metrics(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds, int32_t n_fam,
                     const int32_t *fam_fail, struct dcr_metrics *m);
 
+/* The errors against a genome on the host (include/dcr.h dcr_genome_metrics
+ * states the map, the codes and the tables; the device's k_genome_metrics
+ * gives the same words).  Adds the counts of the four single-strand and the
+ * two duplex records of processed families [0, n_fam) into *m (the caller
+ * zeroes it), skipping the families with fam_fail[f] != 0 when fam_fail is not
+ * NULL.  ss needs pos, n_cig and cigar too.  codes / ref_off / n_ref as
+ * dcr_set_genome takes them (n_ref > 0; checked here as there, the codes as
+ * they are read: a code above 4 counts as 4).  To be called before
+ * dcr_fmt_mate_overlap and dcr_fmt_filter: it counts the consensus as called.
+ * Reads only. */
+struct dcr_genome_metrics;
+int dcr_fmt_genome_metrics(const dcr_host_batch *hb, const dcr_fmt_out *ss, const dcr_fmt_out *ds,
+                           const uint8_t *codes, const int64_t *ref_off, int32_t n_ref, int32_t n_fam,
+                           const int32_t *fam_fail, struct dcr_genome_metrics *m);
+
 /* ---- the GPU BGZF block compressor (csrc/dcr_deflate.h) emulated lane by
  * lane on the host, for tests: one BGZF block of in[0, n) (n <= 0xff00) into
  * out (>= 64 KiB); returns its size or -1 */
